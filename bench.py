@@ -1,12 +1,19 @@
 #!/usr/bin/env python3
 """Headline benchmark (BASELINE.json): imgs/s of the partial-conv inpainting training step
 (ImageFill, 512x512, batch 32 per GPU, train-mode BN, fwd + bwd + gradient all-reduce + fused
-SGD update) on N MI355X of one node, with the roofline of the dominant kernel class, the
-per-class rooflines and the CPU baseline (the oracle timed on the host cores) in the same JSON line.
+SGD update) on N MI355X of one node.  A plain run sets up, warms up, times the steps and prints
+one JSON line; --full adds the roofline of the dominant kernel class, the per-class rooflines,
+the forward-only rate, the other arithmetic modes, the communication figures, the CPU baseline
+(the oracle timed on the host cores) and the secondary configs to the same line.
 
-    python bench.py --gpus 1 --steps 50 --warmup 10
+    python bench.py --gpus 1 --steps 50 --warmup 10 [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
+
+--dump-outputs DIR writes what the last timed step left to its caller as DIR/<name>.npy (float32):
+loss, params (the updated flat parameter buffer), grads (the flat gradient buffer) and bn_buffers
+(the floating-point module buffers: BatchNorm running statistics).  Inputs and initial weights are
+seeded, so two builds run with the same arguments can be compared output for output.
 """
 import argparse
 import hashlib
@@ -217,6 +224,22 @@ def host_cpu():
     return model, phys, os.cpu_count()
 
 
+def cpus_available():
+    """CPUs this process may actually run on: the affinity mask, a cgroup v2 CPU quota and OMP_NUM_THREADS, whichever is
+    smallest (a container can see every core of the host and be allowed a few of them; threads beyond those only contend)"""
+    n = len(os.sched_getaffinity(0)) if hasattr(os, "sched_getaffinity") else (os.cpu_count() or 1)
+    try:
+        quota, period = open("/sys/fs/cgroup/cpu.max").read().split()[:2]
+        if quota != "max":
+            n = min(n, max(1, int(quota) // int(period)))
+    except (OSError, ValueError):
+        pass
+    omp = os.environ.get("OMP_NUM_THREADS", "")
+    if omp.isdigit() and int(omp) > 0:
+        n = min(n, int(omp))
+    return n
+
+
 def cpu_baseline(size: int, threads: int):
     """Oracle (stock-PyTorch CPU restatement of the reference) on a bounded sample of the workload, SURVEY.md 8(d)
     protocol: bs 4, 1 warm-up + 3 timed steps, median."""
@@ -285,9 +308,16 @@ def main(argv=None, return_line=False):
     ap.add_argument("--no-f32-leg", action="store_true", help="skip the short run in the bit-exact f32-MFMA arithmetic mode")
     ap.add_argument("--cpu-threads", type=int, default=0, help="threads for the CPU-baseline leg (default: both min(physical cores, 32) and all physical cores, the better one reported)")
     ap.add_argument("--bernoulli-masks", action="store_true", help="stress variant: i.i.d. per-channel masks")
-    ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg 5 / cfg 3 legs the default headline run appends (secondary_configs)")
+    ap.add_argument("--no-secondary", action="store_true", help="skip the short cfg 5 / cfg 3 legs a --full headline run appends (secondary_configs)")
     ap.add_argument("--graph", action="store_true", help="also replay the step from a HIP graph (measured: no gain; off by default)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything besides the headline figure: HIP events around the GEMM entry points in the timed steps, the per-class pass "
+                         "and rooflines, forward-only rate, f32-MFMA / 3-product legs, communication figures, CPU baseline, secondary configs")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write loss / parameters / gradients / BatchNorm buffers after the last timed step as DIR/<name>.npy (float32)")
     args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -396,19 +426,20 @@ def main(argv=None, return_line=False):
     for _ in range(args.warmup - 1):
         loss = trainer.step(corrupted, mask, clean_nhwc)
     sync()
-    start_timing(gemm_calls)      # HIP events (launch stream) around the GEMM entry points inside the timed region
-    trainer.measure_exposed = world > 1    # N > 1: how long each step stalls for all-reduces backward did not hide (2 events / step)
+    if args.full:
+        start_timing(gemm_calls)      # HIP events (launch stream) around the GEMM entry points inside the timed region
+    trainer.measure_exposed = args.full and world > 1    # N > 1: how long each step stalls for all-reduces backward did not hide (2 events / step)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss = trainer.step(corrupted, mask, clean_nhwc)
     sync()
     elapsed = time.perf_counter() - t0
-    timed = stop_timing()
+    timed = stop_timing() if args.full else {}
     eager_ms = elapsed / args.steps * 1e3
     trainer.measure_exposed = False
     # "comm": bucket layout, stand-alone all-reduce time / bus bandwidth of the whole gradient buffer, and (N > 1) the exposed
     # vs overlapped split of it measured in the timed steps above
-    comm = trainer.comm_stats() if hasattr(trainer, "comm_stats") else None
+    comm = trainer.comm_stats() if args.full and hasattr(trainer, "comm_stats") else None
     graphed = False
     if args.graph:
         try:
@@ -426,6 +457,103 @@ def main(argv=None, return_line=False):
             print(f"[bench] HIP graph capture failed ({type(exc).__name__}: {exc}); reporting the eager loop", file=sys.stderr)
             sync()
     final_loss = float(loss.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, loss, trainer, model)   # before anything below steps the model again
+    if args.full:
+        classes, fwd_steps, fwd_elapsed, f32_leg, split3_leg = full_legs(args, trainer, model, corrupted, mask, clean_nhwc, products, world, sync)
+    if use_dist:
+        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
+        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
+        elapsed = float(tt.item())
+
+    if rank == 0:
+        imgs = world * args.batch * args.steps
+        value = imgs / elapsed
+        if seg:
+            workload = (f"{args.model}{' (pixel-shuffle head)' if args.pixel_shuffle and args.model == 'TextSegament' else ''}"
+                        f"{' (encoder stages recomputed in backward)' if args.checkpoint else ''} {args.size}x{args.size} text-segmentation train step "
+                        f"(fwd+bwd, train-mode BN, BinaryFocalLoss, grad all-reduce, fused SGD), {args.batch} imgs/GPU, synthetic manga tiles")
+            metric = f"imgs/sec fwd+bwd on {args.size}x{args.size} text segmentation ({args.model}; secondary config, not the headline metric)"
+        else:
+            workload = (f"{args.model} {args.size}x{args.size} partial-conv inpainting train step (fwd+bwd, train-mode BN, L1 loss, grad all-reduce, "
+                        f"fused SGD), {args.batch} imgs/GPU, random line/ellipse hole masks")
+            metric = "imgs/sec fwd+bwd on 512x512 partial-conv inpaint"
+        dtype = "bf16 activation / activation-gradient storage (NHWC, 8 channels per 16-byte vector); fp32 accumulation, BatchNorm statistics, parameters and parameter gradients; matrix products bf16 x bf16 -> fp32 (BASELINE config 5 'mixed bf16')" if bf16_storage else {0: "f32", 1: "f32 storage / accumulation / stencils / BatchNorm; matrix products on bf16-rounded operands (the 'mixed bf16' arithmetic of cfg 5)"}.get(
+            products, f"f32 (storage, accumulation, stencils, BatchNorm; matrix products = {products}-term exact bf16 split on the bf16 MFMA, fp32-class error)")
+        line = {
+            "metric": metric,
+            "value": round(value, 2), "unit": "imgs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
+            "vs_baseline": None,
+            "dtype": dtype,
+            "data": "synthetic",
+            "config": {"workload": workload, "global_batch": world * args.batch, "parallelism": f"dp{world}", "gemm_products": products,
+                       "activation_storage": storage_seen},
+            "final_loss": final_loss, "launch": "hip_graph_replay" if graphed else "eager", "eager_ms_per_step": round(eager_ms, 3),
+        }
+        line["peak_mem_gib"] = round(torch.cuda.max_memory_allocated() / 2**30, 1) if on_gpu else None
+        if args.full:
+            ms_per_img = elapsed / imgs * world * 1e3  # per-GPU ms per image
+            line.update(full_fields(args, timed, classes, fwd_steps, fwd_elapsed, f32_leg, split3_leg, comm, products, bf16_storage, world, ms_per_img))
+            if not args.no_cpu_baseline and world == 1 and not seg:
+                _, phys, logical = host_cpu()
+                if args.cpu_threads:
+                    line["cpu_baseline"] = cpu_baseline(args.size, args.cpu_threads)
+                else:
+                    # two thread counts: 32 (where a 4-image batch stops scaling) and every physical core; the better one is the baseline.
+                    # Neither beyond the CPUs this process is allowed (a container may see more cores than it gets)
+                    cores = min(phys or logical or 1, cpus_available())
+                    runs = [cpu_baseline(args.size, t) for t in sorted({min(cores, 32), cores})]
+                    best = max(runs, key=lambda r: r["value"])
+                    best["all_runs"] = [{"cores": r["cores"], "value": r["value"]} for r in runs]
+                    line["cpu_baseline"] = best
+            elif world == 1:
+                line["cpu_baseline"] = None
+        if return_line:
+            return line
+        headline = (args.model == "ImageFill" and args.size == 512 and args.batch == 32 and args.products < 0 and not bf16_storage
+                    and not args.knob and not args.bernoulli_masks)
+        if args.full and headline and world == 1 and on_gpu and not args.no_secondary:
+            # BASELINE configs 5 and 3 through the same code path, short legs (like f32_mfma_mode) so that every --full run times
+            # them; the headline's tensors are released first
+            import gc
+            del model, trainer, corrupted, mask, clean_nhwc, loss
+            gc.collect()
+            torch.cuda.empty_cache()
+            line["secondary_configs"] = {name: secondary_leg(argv2) for name, argv2 in SECONDARY_LEGS.items()}
+        print(json.dumps(line), flush=True)
+    if use_dist:
+        dist.barrier()
+        dist.destroy_process_group()
+
+
+# float32 elements per dumped array: params + grads at their cap, the buffers at theirs and the loss stay under 64 MB in all
+DUMP_CAP = {"params": 7_500_000, "grads": 7_500_000, "bn_buffers": 1 << 20}
+
+
+def dump_outputs(out_dir, loss, trainer, model):
+    """What the last timed step hands its caller, as float32 .npy files: the loss, the updated parameters and the gradients
+    (the trainer's flat buffers, alignment padding included) and the floating-point module buffers.  An array longer than its
+    DUMP_CAP is written as a fixed sample (seeded, sorted indices: the same for every run of the same configuration)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    bufs = [b.detach().reshape(-1).float() for b in model.buffers() if b.is_floating_point()]
+    arrays = {"loss": loss.detach().reshape(1), "params": trainer.flat_param, "grads": trainer.flat_grad,
+              "bn_buffers": torch.cat(bufs) if bufs else torch.zeros(0)}
+    for name, t in arrays.items():
+        a = t.detach().float().cpu().numpy()
+        cap = DUMP_CAP.get(name)
+        if cap is not None and a.size > cap:
+            a = a[np.sort(np.random.default_rng(1234).choice(a.size, cap, replace=False))]
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(a, dtype=np.float32))
+
+
+def full_legs(args, trainer, model, corrupted, mask, clean_nhwc, products, world, sync):
+    """--full: the runs after the timed steps -- the per-class pass, the forward-only rate, the other arithmetic modes"""
+    from text_segmentation_image_inpainting_amd import _lib
+    on_gpu = TEST_RUNTIME is None
+    start_timing = _lib.start_timing if on_gpu else (lambda names: None)
+    stop_timing = _lib.stop_timing if on_gpu else (lambda: {})
     # per-class pass: HIP events around EVERY hot entry point for a few extra steps (outside the timed region: the
     # ~1800 extra event records per step would perturb `value`)
     prof_steps = 3
@@ -470,128 +598,74 @@ def main(argv=None, return_line=False):
         f32_leg = mode_leg(0, "v_mfma_f32_32x32x2_f32 (bit-exact fp32 FMA chain)")
         if products != 3:
             split3_leg = mode_leg(3, "2-piece bf16 split, 3 partial products (dropped terms <= 2^-15 |a*b|; opt-in, NOT the reported arithmetic)")
-    if use_dist:
-        tt = torch.tensor([elapsed], dtype=torch.float64, device=dev)
-        dist.all_reduce(tt, op=dist.ReduceOp.MAX)
-        elapsed = float(tt.item())
+    return classes, fwd_steps, fwd_elapsed, f32_leg, split3_leg
 
-    if rank == 0:
-        imgs = world * args.batch * args.steps
-        value = imgs / elapsed
-        # roofline of the dominant kernel class, from the HIP events of the timed region
-        tt_classes = class_table(timed, args.steps, products)
-        dom = max(tt_classes.items(), key=lambda kv: kv[1]["ms_per_step"]) if tt_classes else None
-        roofline = None
-        if dom:
-            k, d = dom
-            # the kernels behind the class: the persistent producer/consumer kernel takes every 6-product layer with N >= 128 that
-            # tiles evenly (csrc/gemm_pc.hip nt_pc_ok), the block-synchronous split kernel the rest
-            kern = {"gemm_nt": (("tsii::gemm_nt_pc_kernel<", "tsii::gemm_nt_split_kernel<") if products else "tsii::gemm_nt_kernel<2, 2, 2, 2"),
-                    "gemm_tn": ("tsii::gemm_tn_split_kernel<2, 2, 2, 2" if products else "tsii::gemm_tn_kernel<2, 2, 2, 2")}.get(k, "tsii::" + k)
-            if bf16_storage:
-                kern = {"gemm_nt": "tsii::hgemm_nt_kernel<", "gemm_tn": "tsii::hgemm_tn_kernel<", "dw_stencil": "tsii::hdw_conv_kernel< + hdw_dw_kernel<",
-                        "dense_conv": "tsii::hgemm_nt_kernel< (gathered) + hgemm_tn_kernel<", "bn_bwd": "tsii::hbn_bwd_apply_kernel + partial",
-                        "bn_act": "tsii::hbn_apply_kernel"}.get(k, "tsii::" + k)
-            kname = kern if isinstance(kern, str) else " + ".join(x.split("::")[1] + "...>" for x in kern)
-            kname = kname.split("::")[1] + "...>" if "::" in kname else kname
-            t_hbm = d["alg_gb_per_step"] / (PEAK_HBM_TBS * 1e3)            # seconds per step at the HBM peak
-            t_mfma = d["ms_per_step"] * 1e-3 * d.get("mfma_frac", 0.0)      # seconds per step at the MFMA peak of the mode
-            hbm_bound = t_hbm >= t_mfma
-            if args.batch == 32 and args.size == 512 and args.model == "ImageFill":
-                traffic, traffic_src = pmc_traffic(kern)
-            elif bf16_storage and args.model == "XceptionTextSegment" and args.size == 1024 and args.batch == 8 and k == "gemm_nt":
-                # the 1x1 products only: AMODE (5th / 1st template argument) 0 -- the gathered forms of the same kernels are class dense_conv
-                traffic, traffic_src = pmc_traffic(("tsii::hgemm_nt_kernel<2, 2, 2, 4, 0,", "tsii::hgemm_nt_kernel<2, 2, 2, 2, 0,", "tsii::hgemm_nt_kernel<2, 2, 2, 1, 0,",
-                                                    "tsii::hgemm_nt_kernel<4, 1, 1, 1, 0,", "tsii::hgemm_nt_ph_kernel<0,"), PMC_SUMMARY_CFG5, all_files=True)
-            else:
-                traffic, traffic_src = None, "not a profiled configuration"
-            roofline = {"bound": "hbm" if hbm_bound else "mfma", "kernel": kname + " (class " + k + (": 1x1-conv forward + dX GEMMs)" if k == "gemm_nt" else ")"),
-                        "achieved": d["tb_per_s"] * 1e3 if hbm_bound else d["fp32_equiv_tflops"],
-                        "peak": PEAK_HBM_TBS * 1e3 if hbm_bound else d["mfma_peak_fp32_equiv"],
-                        "unit": "GB/s" if hbm_bound else "TFLOP/s (fp32-equivalent)",
-                        "frac": d["hbm_frac"] if hbm_bound else d["mfma_frac"],
-                        "hbm_frac": d["hbm_frac"], "mfma_frac": d.get("mfma_frac"),
-                        # sum over the class's launches of max(HBM time, MFMA time) / measured: each layer against its own bound
-                        "per_launch_roofline_frac": d["per_launch_roofline_frac"],
-                        "traffic": traffic, "traffic_source": traffic_src,
-                        "alg_bytes_per_launch": round(d["alg_gb_per_step"] * 1e9 / max(1, d["launches_per_step"])),
-                        "launches_per_step": d["launches_per_step"],
-                        "avg_launch_ms": round(d["ms_per_step"] / max(1, d["launches_per_step"]), 4),
-                        "ms_per_step_in_class": d["ms_per_step"],
-                        "arithmetic": ("bf16 operands from HBM, one v_mfma_f32_32x32x16_bf16 product per multiply-add, fp32 accumulate, one RNE rounding per stored value" if bf16_storage
-                                       else f"split-bf16: {products} v_mfma_f32_32x32x16_bf16 partial products per fp32 product, fp32 accumulate" if products
-                                       else "v_mfma_f32_32x32x2_f32")}
-        ms_per_img = elapsed / imgs * world * 1e3  # per-GPU ms per image
-        whole = None
-        if (args.model, args.size) in WHOLE_FWD:
-            gf, gb = WHOLE_FWD[(args.model, args.size)]
-            gb = gb / 2 if bf16_storage else gb           # bf16 activation storage: the same tensors at 2 bytes per element
-            flop_peak = PEAK_BF16_TFLOPS if (bf16_storage or products == 1) else PEAK_FP32_TFLOPS     # the arithmetic the mode asks for
-            t_hbm = 3 * gb / (PEAK_HBM_TBS * 1e3) * 1e3
-            t_flop = 3 * gf / (flop_peak * 1e3) * 1e3
-            fwd_ms_per_img = fwd_elapsed / fwd_steps / args.batch * 1e3
-            whole = {"alg_gflop_per_img": round(3 * gf, 1), "alg_gb_per_img": round(3 * gb, 3),
-                     "t_min_ms_per_img_hbm": round(t_hbm, 3),
-                     ("t_min_ms_per_img_bf16_flop" if flop_peak == PEAK_BF16_TFLOPS else "t_min_ms_per_img_fp32_flop"): round(t_flop, 3),
-                     "frac_of_roofline": round(max(t_hbm, t_flop) / ms_per_img, 4),
-                     "frac_of_hbm_roofline": round(t_hbm / ms_per_img, 4),
-                     "forward_frac_of_roofline": round(max(t_hbm, t_flop) / 3 / fwd_ms_per_img, 4),
-                     "forward_frac_of_hbm_roofline": round(t_hbm / 3 / fwd_ms_per_img, 4)}
-        if seg:
-            workload = (f"{args.model}{' (pixel-shuffle head)' if args.pixel_shuffle and args.model == 'TextSegament' else ''}"
-                        f"{' (encoder stages recomputed in backward)' if args.checkpoint else ''} {args.size}x{args.size} text-segmentation train step "
-                        f"(fwd+bwd, train-mode BN, BinaryFocalLoss, grad all-reduce, fused SGD), {args.batch} imgs/GPU, synthetic manga tiles")
-            metric = f"imgs/sec fwd+bwd on {args.size}x{args.size} text segmentation ({args.model}; secondary config, not the headline metric)"
+
+def full_fields(args, timed, classes, fwd_steps, fwd_elapsed, f32_leg, split3_leg, comm, products, bf16_storage, world, ms_per_img):
+    """--full: the fields of the line beyond the headline figure (roofline of the dominant class from the HIP events of the timed
+    steps, per-class table, whole-step roofline, forward-only rate, the other arithmetic modes, communication)"""
+    # roofline of the dominant kernel class, from the HIP events of the timed region
+    tt_classes = class_table(timed, args.steps, products)
+    dom = max(tt_classes.items(), key=lambda kv: kv[1]["ms_per_step"]) if tt_classes else None
+    roofline = None
+    if dom:
+        k, d = dom
+        # the kernels behind the class: the persistent producer/consumer kernel takes every 6-product layer with N >= 128 that
+        # tiles evenly (csrc/gemm_pc.hip nt_pc_ok), the block-synchronous split kernel the rest
+        kern = {"gemm_nt": (("tsii::gemm_nt_pc_kernel<", "tsii::gemm_nt_split_kernel<") if products else "tsii::gemm_nt_kernel<2, 2, 2, 2"),
+                "gemm_tn": ("tsii::gemm_tn_split_kernel<2, 2, 2, 2" if products else "tsii::gemm_tn_kernel<2, 2, 2, 2")}.get(k, "tsii::" + k)
+        if bf16_storage:
+            kern = {"gemm_nt": "tsii::hgemm_nt_kernel<", "gemm_tn": "tsii::hgemm_tn_kernel<", "dw_stencil": "tsii::hdw_conv_kernel< + hdw_dw_kernel<",
+                    "dense_conv": "tsii::hgemm_nt_kernel< (gathered) + hgemm_tn_kernel<", "bn_bwd": "tsii::hbn_bwd_apply_kernel + partial",
+                    "bn_act": "tsii::hbn_apply_kernel"}.get(k, "tsii::" + k)
+        kname = kern if isinstance(kern, str) else " + ".join(x.split("::")[1] + "...>" for x in kern)
+        kname = kname.split("::")[1] + "...>" if "::" in kname else kname
+        t_hbm = d["alg_gb_per_step"] / (PEAK_HBM_TBS * 1e3)            # seconds per step at the HBM peak
+        t_mfma = d["ms_per_step"] * 1e-3 * d.get("mfma_frac", 0.0)      # seconds per step at the MFMA peak of the mode
+        hbm_bound = t_hbm >= t_mfma
+        if args.batch == 32 and args.size == 512 and args.model == "ImageFill":
+            traffic, traffic_src = pmc_traffic(kern)
+        elif bf16_storage and args.model == "XceptionTextSegment" and args.size == 1024 and args.batch == 8 and k == "gemm_nt":
+            # the 1x1 products only: AMODE (5th / 1st template argument) 0 -- the gathered forms of the same kernels are class dense_conv
+            traffic, traffic_src = pmc_traffic(("tsii::hgemm_nt_kernel<2, 2, 2, 4, 0,", "tsii::hgemm_nt_kernel<2, 2, 2, 2, 0,", "tsii::hgemm_nt_kernel<2, 2, 2, 1, 0,",
+                                                "tsii::hgemm_nt_kernel<4, 1, 1, 1, 0,", "tsii::hgemm_nt_ph_kernel<0,"), PMC_SUMMARY_CFG5, all_files=True)
         else:
-            workload = (f"{args.model} {args.size}x{args.size} partial-conv inpainting train step (fwd+bwd, train-mode BN, L1 loss, grad all-reduce, "
-                        f"fused SGD), {args.batch} imgs/GPU, random line/ellipse hole masks")
-            metric = "imgs/sec fwd+bwd on 512x512 partial-conv inpaint"
-        dtype = "bf16 activation / activation-gradient storage (NHWC, 8 channels per 16-byte vector); fp32 accumulation, BatchNorm statistics, parameters and parameter gradients; matrix products bf16 x bf16 -> fp32 (BASELINE config 5 'mixed bf16')" if bf16_storage else {0: "f32", 1: "f32 storage / accumulation / stencils / BatchNorm; matrix products on bf16-rounded operands (the 'mixed bf16' arithmetic of cfg 5)"}.get(
-            products, f"f32 (storage, accumulation, stencils, BatchNorm; matrix products = {products}-term exact bf16 split on the bf16 MFMA, fp32-class error)")
-        line = {
-            "metric": metric,
-            "value": round(value, 2), "unit": "imgs/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 3), "higher_is_better": True, "scaling": "weak",
-            "vs_baseline": None,
-            "dtype": dtype,
-            "data": "synthetic",
-            "config": {"workload": workload, "global_batch": world * args.batch, "parallelism": f"dp{world}", "gemm_products": products,
-                       "activation_storage": storage_seen},
-            "roofline": roofline, "kernel_classes": classes, "whole_step_roofline": whole, "final_loss": final_loss,
-            "launch": "hip_graph_replay" if graphed else "eager", "eager_ms_per_step": round(eager_ms, 3),
+            traffic, traffic_src = None, "not a profiled configuration"
+        roofline = {"bound": "hbm" if hbm_bound else "mfma", "kernel": kname + " (class " + k + (": 1x1-conv forward + dX GEMMs)" if k == "gemm_nt" else ")"),
+                    "achieved": d["tb_per_s"] * 1e3 if hbm_bound else d["fp32_equiv_tflops"],
+                    "peak": PEAK_HBM_TBS * 1e3 if hbm_bound else d["mfma_peak_fp32_equiv"],
+                    "unit": "GB/s" if hbm_bound else "TFLOP/s (fp32-equivalent)",
+                    "frac": d["hbm_frac"] if hbm_bound else d["mfma_frac"],
+                    "hbm_frac": d["hbm_frac"], "mfma_frac": d.get("mfma_frac"),
+                    # sum over the class's launches of max(HBM time, MFMA time) / measured: each layer against its own bound
+                    "per_launch_roofline_frac": d["per_launch_roofline_frac"],
+                    "traffic": traffic, "traffic_source": traffic_src,
+                    "alg_bytes_per_launch": round(d["alg_gb_per_step"] * 1e9 / max(1, d["launches_per_step"])),
+                    "launches_per_step": d["launches_per_step"],
+                    "avg_launch_ms": round(d["ms_per_step"] / max(1, d["launches_per_step"]), 4),
+                    "ms_per_step_in_class": d["ms_per_step"],
+                    "arithmetic": ("bf16 operands from HBM, one v_mfma_f32_32x32x16_bf16 product per multiply-add, fp32 accumulate, one RNE rounding per stored value" if bf16_storage
+                                   else f"split-bf16: {products} v_mfma_f32_32x32x16_bf16 partial products per fp32 product, fp32 accumulate" if products
+                                   else "v_mfma_f32_32x32x2_f32")}
+    whole = None
+    if (args.model, args.size) in WHOLE_FWD:
+        gf, gb = WHOLE_FWD[(args.model, args.size)]
+        gb = gb / 2 if bf16_storage else gb           # bf16 activation storage: the same tensors at 2 bytes per element
+        flop_peak = PEAK_BF16_TFLOPS if (bf16_storage or products == 1) else PEAK_FP32_TFLOPS     # the arithmetic the mode asks for
+        t_hbm = 3 * gb / (PEAK_HBM_TBS * 1e3) * 1e3
+        t_flop = 3 * gf / (flop_peak * 1e3) * 1e3
+        fwd_ms_per_img = fwd_elapsed / fwd_steps / args.batch * 1e3
+        whole = {"alg_gflop_per_img": round(3 * gf, 1), "alg_gb_per_img": round(3 * gb, 3),
+                 "t_min_ms_per_img_hbm": round(t_hbm, 3),
+                 ("t_min_ms_per_img_bf16_flop" if flop_peak == PEAK_BF16_TFLOPS else "t_min_ms_per_img_fp32_flop"): round(t_flop, 3),
+                 "frac_of_roofline": round(max(t_hbm, t_flop) / ms_per_img, 4),
+                 "frac_of_hbm_roofline": round(t_hbm / ms_per_img, 4),
+                 "forward_frac_of_roofline": round(max(t_hbm, t_flop) / 3 / fwd_ms_per_img, 4),
+                 "forward_frac_of_hbm_roofline": round(t_hbm / 3 / fwd_ms_per_img, 4)}
+    return {"roofline": roofline, "kernel_classes": classes, "whole_step_roofline": whole,
             "forward_only": {"value": round(world * args.batch * fwd_steps / fwd_elapsed, 2), "unit": "imgs/s (rank 0 clock)",
                              "ms_per_step": round(fwd_elapsed / fwd_steps * 1e3, 3), "steps": fwd_steps},
-            "f32_mfma_mode": f32_leg, "split3_mode": split3_leg, "comm": comm,
-        }
-        line["peak_mem_gib"] = round(torch.cuda.max_memory_allocated() / 2**30, 1) if on_gpu else None
-        if not args.no_cpu_baseline and world == 1 and not seg:
-            _, phys, logical = host_cpu()
-            if args.cpu_threads:
-                line["cpu_baseline"] = cpu_baseline(args.size, args.cpu_threads)
-            else:
-                # two thread counts: 32 (where a 4-image batch stops scaling) and every physical core; the better one is the baseline
-                runs = [cpu_baseline(args.size, t) for t in sorted({min(phys or logical or 1, 32), phys or logical or 1})]
-                best = max(runs, key=lambda r: r["value"])
-                best["all_runs"] = [{"cores": r["cores"], "value": r["value"]} for r in runs]
-                line["cpu_baseline"] = best
-        elif world == 1:
-            line["cpu_baseline"] = None
-        if return_line:
-            return line
-        headline = (args.model == "ImageFill" and args.size == 512 and args.batch == 32 and args.products < 0 and not bf16_storage
-                    and not args.knob and not args.bernoulli_masks)
-        if headline and world == 1 and on_gpu and not args.no_secondary:
-            # BASELINE configs 5 and 3 through the same code path, short legs (like f32_mfma_mode) so that every default run -- the
-            # driver's included -- times them; the headline's tensors are released first
-            import gc
-            del model, trainer, corrupted, mask, clean_nhwc, loss
-            gc.collect()
-            torch.cuda.empty_cache()
-            line["secondary_configs"] = {name: secondary_leg(argv2) for name, argv2 in SECONDARY_LEGS.items()}
-        print(json.dumps(line), flush=True)
-    if use_dist:
-        dist.barrier()
-        dist.destroy_process_group()
+            "f32_mfma_mode": f32_leg, "split3_mode": split3_leg, "comm": comm}
 
 
 def secondary_leg(argv2, steps=6, warmup=3):
@@ -601,7 +675,8 @@ def secondary_leg(argv2, steps=6, warmup=3):
     import text_segmentation_image_inpainting_amd as T
     torch.cuda.reset_peak_memory_stats()
     try:
-        rec = main(list(argv2) + ["--steps", str(steps), "--warmup", str(warmup), "--no-cpu-baseline", "--no-f32-leg", "--no-secondary"], return_line=True)
+        rec = main(list(argv2) + ["--steps", str(steps), "--warmup", str(warmup), "--full", "--no-cpu-baseline", "--no-f32-leg", "--no-secondary"],
+                   return_line=True)
         out = {"argv": " ".join(argv2), "value": rec["value"], "unit": rec["unit"], "ms_per_step": rec["ms_per_step"], "steps": steps, "warmup": warmup,
                "forward_ms_per_step": rec["forward_only"]["ms_per_step"], "dtype": rec["dtype"], "workload": rec["config"]["workload"],
                "whole_step_roofline": rec["whole_step_roofline"], "roofline": rec["roofline"], "peak_mem_gib": rec["peak_mem_gib"],

@@ -19,16 +19,7 @@ def _free_port():
         return s.getsockname()[1]
 
 
-def _rank(rank, world, port, out, bodies=1, bucket_mb=0.0005):
-    import contextlib
-    import io
-    import sys
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    sys.path.insert(0, root)
-    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
-    torch.set_num_threads(2)
-    import bench
-    from tests.backends import emu_backend
+def _tiny_factory(bodies=1):
     import text_segmentation_image_inpainting_amd as T
     act = torch.nn.LeakyReLU(0.3)
 
@@ -47,11 +38,26 @@ def _rank(rank, world, port, out, bodies=1, bucket_mb=0.0005):
             for blk in self.body:
                 h = blk(h)
             return self.head(h)[0]
+    return Tiny
+
+
+def _rank(rank, world, port, out, bodies=1, bucket_mb=0.0005):
+    import contextlib
+    import io
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    os.environ.update(RANK=str(rank), LOCAL_RANK=str(rank), WORLD_SIZE=str(world), MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    torch.set_num_threads(2)
+    import bench
+    from tests.backends import emu_backend
+    Tiny = _tiny_factory(bodies)
     with emu_backend() as dev:
         bench.TEST_RUNTIME = {"device": dev, "backend": "gloo", "model_factory": Tiny, "trainer_kwargs": {"bucket_mb": bucket_mb}}
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
-            bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "2", "--size", "32", "--no-cpu-baseline", "--no-f32-leg"])
+            bench.main(["--gpus", str(world), "--steps", "2", "--warmup", "1", "--batch", "2", "--size", "32", "--full", "--no-cpu-baseline",
+                        "--no-f32-leg"])
     open(f"{out}.{rank}", "w").write(buf.getvalue())
 
 
@@ -118,7 +124,7 @@ def _rank_seg(rank, world, port, out):
         buf = io.StringIO()
         with contextlib.redirect_stdout(buf):
             bench.main(["--gpus", str(world), "--model", "XceptionTextSegment", "--storage", "bf16", "--steps", "2", "--warmup", "1", "--batch", "2",
-                        "--size", "32", "--no-cpu-baseline"])
+                        "--size", "32", "--full", "--no-cpu-baseline"])
     open(f"{out}.{rank}", "w").write(buf.getvalue())
 
 
@@ -133,3 +139,57 @@ def test_bench_two_ranks_gloo_bf16_storage_segmentation_step():
     assert rec["n_gpus"] == 2 and rec["config"]["activation_storage"] == "bf16" and rec["dtype"].startswith("bf16 activation")
     assert rec["config"]["global_batch"] == 4 and rec["value"] > 0 and rec["comm"]["world"] == 2 and rec["comm"]["allreduce_ms"] > 0
     assert rec["final_loss"] == rec["final_loss"] and rec["final_loss"] > 0          # finite
+
+
+def test_bench_plain_run_and_dump_outputs(tmp_path, monkeypatch):
+    """A plain run (no --full) on one rank: warm-up and exactly --steps timed steps, nothing after them, a line with the headline
+    fields only; --dump-outputs writes the last step's loss / parameters / gradients / BatchNorm buffers as float32, the same in two
+    runs with the same arguments, and a seeded sample of an array longer than its cap."""
+    import contextlib
+    import io
+
+    import numpy as np
+    import bench
+    from tests.backends import emu_backend
+    from text_segmentation_image_inpainting_amd.train_step import FlatSGDTrainer
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
+        monkeypatch.delenv(k, raising=False)
+    calls = []
+    step = FlatSGDTrainer.step
+    monkeypatch.setattr(FlatSGDTrainer, "step", lambda self, *a: calls.append(1) or step(self, *a))
+    torch.set_num_threads(2)
+
+    def run(d):
+        buf = io.StringIO()
+        with contextlib.redirect_stdout(buf):
+            bench.main(["--steps", "3", "--warmup", "2", "--batch", "2", "--size", "32", "--dump-outputs", str(d)])
+        lines = [ln for ln in buf.getvalue().splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        return json.loads(lines[0])
+    try:
+        with emu_backend() as dev:
+            monkeypatch.setattr(bench, "TEST_RUNTIME", {"device": dev, "backend": "gloo", "model_factory": _tiny_factory(1)})
+            rec = run(tmp_path / "a")
+            assert len(calls) == 2 + 3, "warm-up (the first step included) + the timed steps, nothing else"
+            run(tmp_path / "b")
+            monkeypatch.setitem(bench.DUMP_CAP, "params", 100)
+            run(tmp_path / "c")
+    finally:
+        bench.TEST_RUNTIME = None
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["warmup"] == 2 and rec["higher_is_better"] is True and rec["unit"] == "imgs/s"
+    assert abs(rec["value"] - 2 / (rec["ms_per_step"] / 1e3)) <= 0.05 * rec["value"] + 0.01
+    for k in ("roofline", "kernel_classes", "whole_step_roofline", "forward_only", "f32_mfma_mode", "split3_mode", "comm", "cpu_baseline"):
+        assert k not in rec, k
+    names = ("loss", "params", "grads", "bn_buffers")
+    a = {n: np.load(tmp_path / "a" / f"{n}.npy") for n in names}
+    b = {n: np.load(tmp_path / "b" / f"{n}.npy") for n in names}
+    assert sum(os.path.getsize(tmp_path / "a" / f"{n}.npy") for n in names) <= 64 * 2**20
+    for n in names:
+        assert a[n].dtype == np.float32 and a[n].size > 0 and np.isfinite(a[n]).all(), n
+        assert np.array_equal(a[n], b[n]), f"{n}: two runs with the same arguments differ"
+    assert abs(float(a["loss"][0]) - rec["final_loss"]) <= 1e-6 * abs(rec["final_loss"])
+    assert np.abs(a["grads"]).max() > 0 and np.abs(a["bn_buffers"]).max() > 0
+    c = np.load(tmp_path / "c" / "params.npy")
+    assert c.shape == (100,) and np.array_equal(c, a["params"][np.sort(np.random.default_rng(1234).choice(a["params"].size, 100, replace=False))])

@@ -282,12 +282,12 @@ def test_segmentation_two_stage_recipe_gpu():
                                    ["--model", "TextSegament", "--size", "128", "--batch", "2", "--pixel-shuffle", "--checkpoint"],
                                    ["--model", "ImageFill", "--size", "128", "--batch", "2"]])
 def test_bench_line_contract_gpu(extra):
-    """bench.py end to end on small shapes: ONE JSON line with the contract's keys, for the headline workload and for the
+    """bench.py --full end to end on small shapes: ONE JSON line with the contract's keys, for the headline workload and for the
     secondary configs (cfg 3 / cfg 5 flags)."""
     import subprocess
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--no-cpu-baseline"] + extra,
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"] + extra,
                        capture_output=True, text=True, timeout=900)
     assert r.returncode == 0, r.stderr[-2000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
@@ -300,3 +300,31 @@ def test_bench_line_contract_gpu(extra):
     assert d["roofline"]["bound"] in ("hbm", "mfma") and 0 < d["roofline"]["frac"] < 1
     assert d["config"]["gemm_products"] == (1 if "--products" in extra else 6)
     assert ("headline" not in d["metric"]) == (extra[1] == "ImageFill")
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dump_outputs_gpu(tmp_path):
+    """bench.py without --full on a small ImageFill step: one line with the headline fields and none of the --full ones, and
+    --dump-outputs writes the last timed step's loss / parameters / gradients / BatchNorm buffers, identical in two runs."""
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    recs = []
+    for d in ("a", "b"):
+        r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--steps", "3", "--warmup", "2", "--size", "128", "--batch", "2",
+                            "--dump-outputs", str(tmp_path / d)], capture_output=True, text=True, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]
+        assert len(lines) == 1
+        recs.append(json.loads(lines[0]))
+    rec = recs[0]
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in rec, k
+    assert rec["steps"] == 3 and rec["value"] > 0 and abs(rec["value"] - 2 / (rec["ms_per_step"] / 1e3)) <= 0.05 * rec["value"] + 0.01
+    for k in ("roofline", "kernel_classes", "forward_only", "f32_mfma_mode", "comm", "cpu_baseline", "secondary_configs"):
+        assert k not in rec, k
+    for n in ("loss", "params", "grads", "bn_buffers"):
+        a, b = np.load(tmp_path / "a" / f"{n}.npy"), np.load(tmp_path / "b" / f"{n}.npy")
+        assert a.dtype == np.float32 and a.size > 0 and np.isfinite(a).all(), n
+        assert np.array_equal(a, b), f"{n}: two runs with the same arguments differ"
+    assert float(np.load(tmp_path / "a" / "loss.npy")[0]) == rec["final_loss"] == recs[1]["final_loss"]
