@@ -1,0 +1,86 @@
+#!/usr/bin/env python3
+"""Remove the text from comic pages: segment -> mask -> inpaint (the reference README's road) with ``TextEraser``.
+Pages of any size are tiled on the device; only the tiles that contain text go through the inpainting net.
+Needs an MI355X (the models have no CPU path).
+
+    python examples/erase_text.py --img-folder pages [--seg-checkpoint seg.pt] [--fill-checkpoint fill.pt] [--out-folder out]
+    python examples/erase_text.py --synthetic            # seeded manga-like page, random-init weights
+
+Writes ``<name>_clean.png`` and ``<name>_mask.png`` (255 = text) per page; ``--synthetic`` also writes the page itself.
+"""
+import argparse
+import os
+import sys
+import tempfile
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+from PIL import Image  # noqa: E402
+
+EXTENSIONS = (".png", ".jpg", ".jpeg", ".bmp", ".webp")
+
+
+def synthetic_page(h, w, seed=0):
+    """a seeded manga-like page of h x w pixels cut from one square synthetic tile"""
+    from text_segmentation_image_inpainting_amd.synthetic import manga_tile
+    side = max(h, w)
+    tile = manga_tile(side, np.random.default_rng(seed)).transpose(1, 2, 0)
+    return np.ascontiguousarray((tile[:h, :w] * 255).astype(np.uint8))
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
+    ap.add_argument("--img-folder", default=None)
+    ap.add_argument("--out-folder", default=None, help="default: next to the inputs (a temporary folder with --synthetic)")
+    ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--synthetic-size", type=int, nargs=2, default=(1170, 1654), metavar=("H", "W"))
+    ap.add_argument("--seg-model", default="XceptionTextSegment", choices=["XceptionTextSegment", "TextSegament"])
+    ap.add_argument("--fill-model", default="ImageFill", choices=["ImageFill", "ImageFillOrigin", "ImageFillOriginV2"])
+    ap.add_argument("--seg-checkpoint", default=None)
+    ap.add_argument("--fill-checkpoint", default=None)
+    ap.add_argument("--tile", type=int, default=512)
+    ap.add_argument("--halo", type=int, default=64)
+    ap.add_argument("--dilate", type=int, default=3)
+    ap.add_argument("--threshold", type=float, default=0.5)
+    ap.add_argument("--tile-batch", type=int, default=8)
+    args = ap.parse_args(argv)
+    import text_segmentation_image_inpainting_amd as T
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    nets = []
+    for name, ckpt in ((args.seg_model, args.seg_checkpoint), (args.fill_model, args.fill_checkpoint)):
+        net = getattr(T, name)()
+        if ckpt:
+            net.load_state_dict(torch.load(ckpt, map_location="cpu"))      # the tolerant loader: reports and skips what does not fit
+        nets.append(net.to(dev).eval())
+    eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
+                          tile_batch=args.tile_batch)
+    if args.synthetic or args.img_folder is None:
+        out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
+        os.makedirs(out_folder, exist_ok=True)
+        page = synthetic_page(*args.synthetic_size)
+        Image.fromarray(page).save(os.path.join(out_folder, "synthetic.png"))
+        pages = [("synthetic", page)]
+    else:
+        out_folder = args.out_folder or args.img_folder
+        os.makedirs(out_folder, exist_ok=True)
+        names = sorted(f for f in os.listdir(args.img_folder) if f.lower().endswith(EXTENSIONS)
+                       and not f.endswith(("_clean.png", "_mask.png")))
+        pages = ((os.path.splitext(f)[0], np.asarray(Image.open(os.path.join(args.img_folder, f)).convert("RGB"))) for f in names)
+    t0 = time.time()
+    for name, page in pages:
+        clean, mask = eraser(page)
+        Image.fromarray(clean).save(os.path.join(out_folder, name + "_clean.png"))
+        Image.fromarray(mask).save(os.path.join(out_folder, name + "_mask.png"))
+        st = eraser.last_stats
+        print("%s: %d x %d, %d of %d tiles inpainted, text fraction %.4f" %
+              (name, page.shape[0], page.shape[1], st["selected"], st["tiles"], float((mask > 0).mean())))
+    print("Runtime :{:.3f} s -> {}".format(time.time() - t0, out_folder))
+
+
+if __name__ == "__main__":
+    main()

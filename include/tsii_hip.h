@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 5
+#define TSII_ABI_VERSION 6
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -525,6 +525,48 @@ int tsii_bf16_from_f32(const float* src, int64_t numel, uint16_t* dst, void* str
 int tsii_bf16_to_f32(const uint16_t* src, int64_t numel, float* dst, void* stream);
 int tsii_bf16_channel_to_f32(const uint16_t* src, int64_t m, int c, int ch, float* dst, void* stream);
 int tsii_bf16_channel_from_f32(const float* src, int64_t m, int c, int ch, uint16_t* dst, void* stream);
+
+/* ---- K8: page pipeline -- text removal on a whole page (the reference README's road: text mask -> white the words out -> inpaint;
+ * the only reference semantics used are Examples/demo_segmentation.py:33-35, sigmoid > 0.5 and MaxPool2d(3, 1, 1)) ----------------
+ * The exceptions to "fp32 everywhere": the page, the text plane and the results are uint8, counts and tile lists int32.
+ * Tiling.  S = tile - 2*halo > 0, tile % 32 == 0.  The page [h,w] is cut into ty*tx = ceil(h/S)*ceil(w/S) square tiles, row-major;
+ * tile (i,j) covers page rows [i*S - halo, i*S - halo + tile) and the same for columns; its CORE is rows [i*S, (i+1)*S) x columns
+ * [j*S, (j+1)*S) clipped to the page.  The cores partition the page: every page pixel is OWNED by exactly one tile, and whatever is
+ * said per page pixel below (its logit, its filler output) is the value at that pixel in its owning tile.
+ * tsii_page_tile_count: ty*tx (0: geometry refused -- h, w >= 1, h*w and the tile volume within 2^31). */
+int tsii_page_tile_count(int h, int w, int tile, int halo);
+
+/* Segmenter tiles: page uint8 [h,w,3] -> tiles fp32 NHWC [ty*tx, tile, tile, 3] (16-byte aligned),
+ *   tiles[t,r,q,c] = fmaf((float)page[ry,rx,c], scale_c, shift_c),   (ry, rx) = the tile coordinate mirrored into the page.
+ * Mirror reflection does not repeat the edge (period 2*(h-1), applied until the coordinate is inside; a side of 1 maps to 0).
+ * For ImageNet-style normalisation the caller passes scale = 1/(255*std), shift = -mean/std. */
+int tsii_page_tiles_norm(const uint8_t* page, int h, int w, int tile, int halo,
+                         float scale0, float scale1, float scale2, float shift0, float shift1, float shift2,
+                         float* tiles, void* stream);
+
+/* Text mask: logits fp32 [ty*tx, tile, tile] (the segmenter's [N,1,T,T]) -> text uint8 [h,w] (1 = text), core_count int32 [ty*tx].
+ *   text0 = logit > logit_threshold                       (log(p/(1-p)) for a probability threshold p; 0 = the demo's sigmoid > 0.5)
+ *   text  = binary dilation of text0 by a dilate x dilate square, outside the page = no text   (dilate odd, 1..31; 3 = MaxPool2d(3,1,1))
+ *   core_count[t] = number of text pixels in the core of tile t -- integer atomics: independent of block order.
+ * core_count is cleared by the call itself. */
+int tsii_tiles_text_mask(const float* logits, int h, int w, int tile, int halo, float logit_threshold, int dilate,
+                         uint8_t* text, int* core_count, void* stream);
+
+/* Filler tiles for the n_sel tiles listed in tile_ids (device int32, tile numbers in [0, ty*tx)):
+ *   mask[k,r,q]  = inside the page ? 1 - text : 0                                     fp32 [n_sel, tile, tile]
+ *   img[k,r,q,c] = ((float)page[y,x,c] / 255.0f) * mask[k,r,q]  (0 outside the page)   fp32 NHWC [n_sel, tile, tile, 3]
+ * -- an IEEE (correctly rounded) fp32 division, then an exact product with 0 / 1; not normalised (Dataloader.py:103-132).
+ * Outside the page is a hole, not a reflection: the partial convolution's own border rule (padding counts as hole, K1). */
+int tsii_page_tiles_fill(const uint8_t* page, const uint8_t* text, int h, int w, int tile, int halo,
+                         const int* tile_ids, int n_sel, float* img, float* mask, void* stream);
+
+/* Compose: clean uint8 [h,w,3], mask_u8 uint8 [h,w] = text * 255.
+ *   clean = text ? (uint8) floorf(fmaf(min(max(out, 0), 1), 255, 0.5)) : page        -- bytes outside text are copied untouched
+ * out: the filler's output fp32 NHWC [n_sel, tile, tile, 3]; slot: device int32 [ty*tx], the index of each tile in out or -1 (a text
+ * pixel whose owning tile has no slot keeps its page byte).  out == slot == NULL with n_sel == 0: a page without text.
+ * The four byte planes are 4-byte aligned. */
+int tsii_compose_page_u8(const uint8_t* page, const uint8_t* text, const float* out, const int* slot, int n_sel,
+                         int h, int w, int tile, int halo, uint8_t* clean, uint8_t* mask_u8, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 5           # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 6           # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -141,6 +141,12 @@ SIGNATURES = {
     "tsii_bf16_to_f32": (_i, [_p, _l, _p, _p]),
     "tsii_bf16_channel_to_f32": (_i, [_p, _l, _i, _i, _p, _p]),
     "tsii_bf16_channel_from_f32": (_i, [_p, _l, _i, _i, _p, _p]),
+    # K8 page pipeline (csrc/pipeline.hip): uint8 page / text planes, int32 counts and tile lists
+    "tsii_page_tile_count": (_i, [_i, _i, _i, _i]),
+    "tsii_page_tiles_norm": (_i, [_p, _i, _i, _i, _i, _f, _f, _f, _f, _f, _f, _p, _p]),
+    "tsii_tiles_text_mask": (_i, [_p, _i, _i, _i, _i, _f, _i, _p, _p, _p]),
+    "tsii_page_tiles_fill": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "tsii_compose_page_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 _LIB = None

@@ -1,0 +1,235 @@
+"""Page-level text removal: segment -> mask -> inpaint -> compose (the reference README's road, run end to end).
+
+``TextEraser`` cuts a uint8 page of any size into overlapping square tiles, runs a segmentation net on them, turns the logits
+into a dilated text plane, sends only the tiles that contain text through an inpainting net, and writes the inpainted pixels back
+into the page bytes.  The page is uploaded once as uint8 and downloaded once as uint8; everything between stays on the device, in
+the four kernels of ``csrc/pipeline.hip`` (semantics: ``include/tsii_hip.h``, "K8: page pipeline") and the two nets.  Inference
+only: nothing here records autograd.
+"""
+from contextlib import contextmanager
+from typing import NamedTuple
+
+import numpy as np
+import torch
+from torch import nn
+
+from . import _lib
+from ._lib import call, ptr
+from .BaseModels import to_nhwc
+from .masks import MaskParts
+
+
+class TileGrid(NamedTuple):
+    """Tiling of an ``h x w`` page: ``ty * tx`` tiles of ``tile`` pixels a side in row-major order; tile ``(i, j)`` starts at page
+    row ``i * stride - halo`` / column ``j * stride - halo`` and owns the core ``[i * stride, (i + 1) * stride)`` x
+    ``[j * stride, (j + 1) * stride)`` clipped to the page."""
+    h: int
+    w: int
+    tile: int
+    halo: int
+    stride: int
+    ty: int
+    tx: int
+
+    @property
+    def count(self):
+        return self.ty * self.tx
+
+    def origin(self, t):
+        """Page (row, column) of the first pixel of tile ``t`` (negative on the first row / column of tiles when halo > 0)."""
+        return (t // self.tx) * self.stride - self.halo, (t % self.tx) * self.stride - self.halo
+
+    def core(self, t):
+        """(y0, y1, x0, x1): the page pixels tile ``t`` owns."""
+        i, j = t // self.tx, t % self.tx
+        return (i * self.stride, min((i + 1) * self.stride, self.h), j * self.stride, min((j + 1) * self.stride, self.w))
+
+
+def tile_grid(h, w, tile, halo) -> TileGrid:
+    h, w, tile, halo = int(h), int(w), int(tile), int(halo)
+    if h < 1 or w < 1:
+        raise ValueError(f"page of {h} x {w} pixels")
+    if tile < 32 or tile % 32 or halo < 0 or tile - 2 * halo <= 0:
+        raise ValueError(f"tile {tile} must be a multiple of 32 and larger than 2 * halo ({halo})")
+    s = tile - 2 * halo
+    return TileGrid(h, w, tile, halo, s, -(-h // s), -(-w // s))
+
+
+# ---- thin wrappers of the tsii_* entry points (no autograd; byte planes are uint8, counts / tile lists int32) ----------------------
+def _same_device(*ts):
+    # no CPU path: host tensors are refused here (the empty fp32 tensor carries the device of the byte / int planes into the check)
+    _lib.check_device(ts[0].new_empty(0, dtype=torch.float32), *[t for t in ts if t.is_floating_point()])
+    assert all(t.device == ts[0].device and t.is_contiguous() for t in ts)
+
+
+def _page_tiles_norm(page, g: TileGrid, scale, shift):
+    tiles = torch.empty((g.count, g.tile, g.tile, 3), dtype=torch.float32, device=page.device)
+    _same_device(page, tiles)
+    call("tsii_page_tiles_norm", ptr(page), g.h, g.w, g.tile, g.halo, *[float(v) for v in scale], *[float(v) for v in shift],
+         ptr(tiles), _lib.stream())
+    return tiles
+
+
+def _tiles_text_mask(logits, g: TileGrid, logit_threshold, dilate):
+    assert logits.shape == (g.count, g.tile, g.tile)
+    text = torch.empty((g.h, g.w), dtype=torch.uint8, device=logits.device)
+    counts = torch.empty((g.count,), dtype=torch.int32, device=logits.device)
+    _same_device(logits, text, counts)
+    call("tsii_tiles_text_mask", ptr(logits), g.h, g.w, g.tile, g.halo, float(logit_threshold), int(dilate), ptr(text), ptr(counts),
+         _lib.stream())
+    return text, counts
+
+
+def _page_tiles_fill(page, text, g: TileGrid, tile_ids):
+    ns = int(tile_ids.numel())
+    img = torch.empty((ns, g.tile, g.tile, 3), dtype=torch.float32, device=page.device)
+    mask = torch.empty((ns, g.tile, g.tile), dtype=torch.float32, device=page.device)
+    _same_device(img, mask, page, text, tile_ids)
+    call("tsii_page_tiles_fill", ptr(page), ptr(text), g.h, g.w, g.tile, g.halo, ptr(tile_ids), ns, ptr(img), ptr(mask), _lib.stream())
+    return img, mask
+
+
+def _compose_page_u8(page, text, out, slot, g: TileGrid, clean, mask_u8):
+    ns = 0 if out is None else int(out.shape[0])
+    assert out is None or out.shape == (ns, g.tile, g.tile, 3)
+    _same_device(page, text, clean, mask_u8, *([] if out is None else [out, slot]))
+    call("tsii_compose_page_u8", ptr(page), ptr(text), ptr(out), ptr(slot), ns, g.h, g.w, g.tile, g.halo, ptr(clean), ptr(mask_u8),
+         _lib.stream())
+
+
+def logit_of(threshold) -> float:
+    """float32 ``log(p / (1 - p))``: the logit threshold ``TextEraser`` hands to ``tsii_tiles_text_mask`` (0 at p = 0.5)."""
+    return float(np.log(np.float32(threshold) / (np.float32(1.0) - np.float32(threshold)), dtype=np.float32))
+
+
+@contextmanager
+def _eval_mode(*nets):
+    """``eval()`` for the call, every sub-module's ``training`` flag put back afterwards (also when the call raises)."""
+    saved = [(m, m.training) for net in nets if isinstance(net, nn.Module) for m in net.modules()]
+    for net in nets:
+        if isinstance(net, nn.Module):
+            net.eval()
+    try:
+        yield
+    finally:
+        for m, flag in saved:
+            m.training = flag
+
+
+class TextEraser:
+    """``clean_u8, mask_u8 = TextEraser(segmenter, filler, ...)(page_u8)``.
+
+    ``segmenter``: callable ``x[N,3,T,T] -> logits[N,1,T,T]`` (``TextSegament``, ``XceptionTextSegment``); ``x`` is the page
+    normalised with ``mean`` / ``std``, mirror-extended beyond the page edges, fp32 in channels-last memory.
+    ``filler``: callable taking ONE argument, the pair ``(x[N,3,T,T], mask)``, and returning ``out[N,3,T,T]`` -- the calling
+    convention of ``ImageFill`` / ``ImageFillOrigin`` / ``ImageFillOriginV2``.  ``x`` is ``page / 255 * mask`` (not normalised,
+    as the inpainting data set feeds it), ``mask`` a 3-channel ``MaskParts`` over one ``[N,T,T]`` plane: 1 = keep, 0 = hole
+    (text, or beyond the page edge).  Both are called under ``torch.no_grad()``; modules run in ``eval()`` mode for the call.
+
+    ``tile`` (multiple of 32) and ``halo``: tiles of ``tile`` pixels a side step by ``tile - 2 * halo``, each owns that core and
+    sees ``halo`` pixels of context around it.  ``threshold`` is the text probability (``sigmoid(logit) > threshold``), ``dilate``
+    the side of the square the text is grown by (odd, 1..31).  Tiles without text in their core skip the filler
+    (``skip_blank_tiles=False`` sends all of them); selected tiles go to it in row-major order, ``tile_batch`` at a time.
+
+    The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
+    the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
+    ``clean`` equals the page wherever ``mask`` is 0.
+    """
+
+    def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
+                 threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True):
+        tile_grid(1, 1, tile, halo)                     # validates tile / halo
+        if not 0.0 < float(threshold) < 1.0:
+            raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
+        if int(dilate) != dilate or not 1 <= dilate <= 31 or dilate % 2 == 0:
+            raise ValueError(f"dilate {dilate} must be odd, 1..31")
+        if int(tile_batch) < 1:
+            raise ValueError("tile_batch >= 1")
+        self.segmenter, self.filler = segmenter, filler
+        self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
+        self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
+        mean32, std32 = np.asarray(mean, np.float32).reshape(3), np.asarray(std, np.float32).reshape(3)
+        self.scale = np.float32(1.0) / (np.float32(255.0) * std32)                       # float32 throughout
+        self.shift = -mean32 / std32
+        self.logit_threshold = logit_of(threshold)
+        if device is None:
+            p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
+            device = p.device if p is not None else torch.device("cuda:0")
+        self.device = torch.device(device)
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page
+
+    # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
+    def _upload(self, page):
+        t = torch.from_numpy(np.ascontiguousarray(page)) if isinstance(page, np.ndarray) else page
+        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
+            raise ValueError(f"page must be [H, W, 3] uint8, got {tuple(t.shape)} {t.dtype}")
+        return t.to(self.device).contiguous()
+
+    def _segment(self, page_d, g):
+        tiles = _page_tiles_norm(page_d, g, self.scale, self.shift)
+        x = tiles.permute(0, 3, 1, 2)                   # [N,3,T,T] view in channels-last memory: to_nhwc() inside the nets is free
+        logits = None
+        for b0 in range(0, g.count, self.tile_batch):
+            lb = self.segmenter(x[b0:b0 + self.tile_batch])
+            n = min(self.tile_batch, g.count - b0)
+            if tuple(lb.shape) != (n, 1, g.tile, g.tile):
+                raise ValueError(f"segmenter returned {tuple(lb.shape)} for {n} tiles of {g.tile}")
+            lb = lb.reshape(n, g.tile, g.tile)
+            if n == g.count:                            # one batch: no gather copy
+                logits = lb.float().contiguous()
+            else:
+                if logits is None:
+                    logits = torch.empty((g.count, g.tile, g.tile), dtype=torch.float32, device=self.device)
+                logits[b0:b0 + n].copy_(lb)             # bf16 logits (bf16 activation storage) are cast here, once
+        return logits
+
+    def _fill(self, page_d, text, g, selected):
+        ids = torch.tensor(selected, dtype=torch.int32).to(self.device)
+        slot_h = np.full(g.count, -1, np.int32)
+        slot_h[selected] = np.arange(len(selected), dtype=np.int32)
+        slot = torch.from_numpy(slot_h).to(self.device)
+        img, mplane = _page_tiles_fill(page_d, text, g, ids)
+        x = img.permute(0, 3, 1, 2)
+        ns, out = len(selected), None
+        for b0 in range(0, ns, self.tile_batch):
+            n = min(self.tile_batch, ns - b0)
+            ob = self.filler((x[b0:b0 + n], MaskParts.from_plane(mplane[b0:b0 + n], 3)))
+            if tuple(ob.shape) != (n, 3, g.tile, g.tile):
+                raise ValueError(f"filler returned {tuple(ob.shape)} for {n} tiles of {g.tile}")
+            if n == ns:
+                out = to_nhwc(ob.float())
+            else:
+                if out is None:
+                    out = torch.empty((ns, g.tile, g.tile, 3), dtype=torch.float32, device=self.device)
+                out[b0:b0 + n].copy_(ob.permute(0, 2, 3, 1))
+        return out, slot
+
+    def _erase(self, page):
+        page_d = self._upload(page)
+        h, w = int(page_d.shape[0]), int(page_d.shape[1])
+        g = tile_grid(h, w, self.tile, self.halo)
+        with torch.no_grad(), _eval_mode(self.segmenter, self.filler):
+            logits = self._segment(page_d, g)
+            text, counts = _tiles_text_mask(logits, g, self.logit_threshold, self.dilate)
+            counts_h = counts.cpu().numpy()             # the one synchronisation before the download
+            selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
+            any_text = bool(counts_h.sum() > 0)
+            out, slot = self._fill(page_d, text, g, selected) if (selected and any_text) else (None, None)
+            off = (h * w * 3 + 15) // 16 * 16           # clean + mask in one buffer (one download); the kernel wants both 4-byte aligned
+            both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
+            clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
+            _compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
+        self.last_stats = {"tiles": g.count, "selected": len(selected) if out is not None else 0, "text_pixels": int(counts_h.sum())}
+        if isinstance(page, np.ndarray):
+            both_h = both.cpu().numpy()
+            return both_h[:h * w * 3].reshape(h, w, 3), both_h[off:].reshape(h, w)
+        if page.device != self.device:
+            both = both.to(page.device)
+            clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
+        return clean, mask_u8
+
+    def __call__(self, page):
+        if isinstance(page, (list, tuple)):
+            return [self._erase(p) for p in page]
+        return self._erase(page)
+

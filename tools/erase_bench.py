@@ -1,0 +1,202 @@
+#!/usr/bin/env python3
+"""Times one page through TextEraser stage by stage (HIP events on the launch stream) and prints one JSON line.
+
+    python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
+
+Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
+tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
+the shapes.  Random-init weights put no meaningful text on a page, so the segmenter's logits are timed as they are and then
+REPLACED by a synthetic logit field (rectangular text blobs over ``--text-fraction`` of the page) for the stages behind it: what is
+timed is the cost of the pipeline, not the quality of a net.  For comparison, in the same run:
+* the mask stage the way examples/demo_segmentation.py does it (download the logits, threshold and nine torch.maximum on the CPU);
+* a torch restatement of the tile, mask and compose stages on the device;
+* the whole page with and without tile selection (pages / s, host clock around synchronised calls).
+"""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+import torch.nn.functional as F  # noqa: E402
+
+
+def blob_logits(g, fraction, seed, dev):
+    """per-tile logits [nt, T, T] of a page whose text is rectangular blobs covering about ``fraction`` of it"""
+    rng = np.random.default_rng(seed)
+    page = np.full((g.h, g.w), -4.0, np.float32)
+    target, covered = fraction * g.h * g.w, 0
+    while covered < target:
+        bh, bw = int(rng.integers(30, 120)), int(rng.integers(60, 300))
+        y, x = int(rng.integers(0, max(1, g.h - bh))), int(rng.integers(0, max(1, g.w - bw)))
+        page[y:y + bh, x:x + bw] = 4.0
+        covered += bh * bw
+    ext = np.pad(page, ((g.halo, g.ty * g.stride + g.halo), (g.halo, g.tx * g.stride + g.halo)), mode="edge")
+    tiles = np.stack([ext[i * g.stride:i * g.stride + g.tile, j * g.stride:j * g.stride + g.tile]
+                      for i in range(g.ty) for j in range(g.tx)])
+    return torch.from_numpy(tiles).to(dev)
+
+
+def main(argv=None):
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, nargs=2, default=(1170, 1654), metavar=("H", "W"))
+    ap.add_argument("--tile", type=int, default=512)
+    ap.add_argument("--halo", type=int, default=64)
+    ap.add_argument("--dilate", type=int, default=3)
+    ap.add_argument("--tile-batch", type=int, default=8)
+    ap.add_argument("--seg-model", default="XceptionTextSegment")
+    ap.add_argument("--fill-model", default="ImageFill")
+    ap.add_argument("--text-fraction", type=float, default=0.1)
+    ap.add_argument("--repeats", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=3)
+    args = ap.parse_args(argv)
+    import text_segmentation_image_inpainting_amd as T
+    from text_segmentation_image_inpainting_amd import pipeline as P
+    from text_segmentation_image_inpainting_amd.synthetic import manga_tile
+    assert torch.cuda.is_available(), "erase_bench needs an MI355X"
+    dev = torch.device("cuda:0")
+    torch.manual_seed(0)
+    seg, fil = getattr(T, args.seg_model)().to(dev).eval(), getattr(T, args.fill_model)().to(dev).eval()
+    h, w = args.size
+    page = np.ascontiguousarray((manga_tile(max(h, w), np.random.default_rng(0)).transpose(1, 2, 0)[:h, :w] * 255).astype(np.uint8))
+    g = P.tile_grid(h, w, args.tile, args.halo)
+    logits_fixed = blob_logits(g, args.text_fraction, 1, dev)
+
+    def make(select):
+        er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
+                          skip_blank_tiles=select)
+        net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
+        er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]
+        return er
+    eraser = make(True)
+
+    ev = lambda: torch.cuda.Event(enable_timing=True)
+    stages = ["upload", "page_tiles_norm", "segmenter", "tiles_text_mask", "counts_d2h", "page_tiles_fill", "filler", "compose_page_u8", "download"]
+
+    def one_page():
+        marks = [ev() for _ in range(len(stages) + 2)]
+        page_pinned = torch.from_numpy(page)
+        with torch.no_grad():
+            marks[0].record()
+            page_d = page_pinned.to(dev)
+            marks[1].record()
+            tiles = P._page_tiles_norm(page_d, g, eraser.scale, eraser.shift)
+            marks[2].record()
+            x = tiles.permute(0, 3, 1, 2)
+            for b in range(0, g.count, args.tile_batch):
+                seg(x[b:b + args.tile_batch])
+            marks[3].record()
+            text, counts = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)
+            marks[4].record()
+            counts_h = counts.cpu().numpy()
+            marks[5].record()
+            selected = [t for t in range(g.count) if counts_h[t] > 0]
+            ids = torch.tensor(selected, dtype=torch.int32).to(dev)
+            slot_h = np.full(g.count, -1, np.int32)
+            slot_h[selected] = np.arange(len(selected), dtype=np.int32)
+            slot = torch.from_numpy(slot_h).to(dev)
+            marks[10].record()                              # the two small uploads above belong to no stage
+            img, mplane = P._page_tiles_fill(page_d, text, g, ids)
+            marks[6].record()
+            xi = img.permute(0, 3, 1, 2)
+            outs = [P.to_nhwc(fil((xi[b:b + args.tile_batch], P.MaskParts.from_plane(mplane[b:b + args.tile_batch], 3))))
+                    for b in range(0, len(selected), args.tile_batch)]
+            out = outs[0] if len(outs) == 1 else torch.cat(outs)
+            marks[7].record()
+            clean, mask_u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev), torch.empty((h, w), dtype=torch.uint8, device=dev)
+            P._compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
+            marks[8].record()
+            clean.cpu(), mask_u8.cpu()
+            marks[9].record()
+        torch.cuda.synchronize()
+        t = [marks[i].elapsed_time(marks[i + 1]) for i in range(len(stages))]
+        t[5] = marks[10].elapsed_time(marks[6])
+        return t, len(selected), int(counts_h.sum()), (page_d, text, out, slot, tiles)
+
+    for _ in range(args.warmup):
+        one_page()
+    runs = [one_page() for _ in range(args.repeats)]
+    n_sel, n_text, keep = runs[0][1], runs[0][2], runs[0][3]
+    ms = {s: [r[0][i] for r in runs] for i, s in enumerate(stages)}
+    med = {s: statistics.median(v) for s, v in ms.items()}
+
+    # bytes each kernel has to move ("page pipeline")
+    npx, tpx = h * w, args.tile * args.tile
+    bytes_ = {"page_tiles_norm": 3 * npx + 12 * g.count * tpx, "tiles_text_mask": 5 * npx,
+              "page_tiles_fill": 4 * npx * n_sel / g.count + 16 * n_sel * tpx, "compose_page_u8": 8 * npx + 12 * n_text}
+
+    def timed(fn, sync=True):
+        for _ in range(args.warmup):
+            fn()
+        vals = []
+        for _ in range(args.repeats):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            fn()
+            if sync:
+                torch.cuda.synchronize()
+            vals.append((time.perf_counter() - t0) * 1e3)
+        return {"median_ms": round(statistics.median(vals), 4), "min_ms": round(min(vals), 4), "max_ms": round(max(vals), 4)}
+
+    page_d, text, out, slot, tiles = keep
+    # (a) the parent's route for the mask stage: the page's logits to the host, threshold + 3 x 3 max-pool with nine torch.maximum
+    stitched = torch.randn(1, 1, h, w, device=dev)
+
+    def demo_mask():
+        m = (stitched > 0).cpu()
+        p = F.pad(m.float(), (1, 1, 1, 1), value=0)
+        o = torch.zeros_like(m, dtype=torch.float32)
+        for dy in range(3):
+            for dx in range(3):
+                o = torch.maximum(o, p[..., dy:dy + h, dx:dx + w])
+        return o.byte()
+
+    # (b) torch restatements on the device
+    iy = torch.from_numpy(np.stack([np.arange(t // g.tx * g.stride - g.halo, t // g.tx * g.stride - g.halo + g.tile) for t in range(g.count)])).to(dev)
+    ix = torch.from_numpy(np.stack([np.arange(t % g.tx * g.stride - g.halo, t % g.tx * g.stride - g.halo + g.tile) for t in range(g.count)])).to(dev)
+
+    def refl(v, n):
+        p = 2 * (n - 1)
+        v = torch.remainder(v, p)
+        return torch.where(v < n, v, p - v)
+    ry, rx = refl(iy, h), refl(ix, w)
+    scale, shift = torch.from_numpy(eraser.scale).to(dev), torch.from_numpy(eraser.shift).to(dev)
+
+    def torch_norm():
+        return page_d[ry[:, :, None], rx[:, None, :]].float() * scale + shift
+
+    def torch_mask():
+        return F.max_pool2d((stitched > 0).float(), args.dilate, 1, args.dilate // 2).byte()
+
+    filled = torch.rand(h, w, 3, device=dev)
+
+    def torch_compose():
+        return torch.where(text[..., None] > 0, torch.floor(filled.clamp(0, 1) * 255 + 0.5).byte(), page_d), text * 255
+
+    result = {
+        "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
+        "seg_model": args.seg_model, "fill_model": args.fill_model, "tiles": g.count, "selected_tiles": n_sel,
+        "text_fraction": round(n_text / npx, 4), "repeats": args.repeats, "warmup": args.warmup,
+        "stage_ms": {s: {"median": round(med[s], 4), "min": round(min(v), 4), "max": round(max(v), 4)} for s, v in ms.items()},
+        "kernel_gb": {k: round(v / 1e9, 5) for k, v in bytes_.items()},
+        "kernel_tb_per_s": {k: round(v / (med[k] * 1e-3) / 1e12, 3) for k, v in bytes_.items()},
+        "kernels_share_of_nets": round(sum(med[k] for k in bytes_) / (med["segmenter"] + med["filler"]), 5),
+        "demo_route_mask_stage": timed(demo_mask, sync=False),
+        "torch_on_device": {"page_tiles_norm": timed(torch_norm), "tiles_text_mask": timed(torch_mask), "compose_page_u8": timed(torch_compose)},
+    }
+    for name, select in (("with_selection", True), ("without_selection", False)):
+        er = make(select)
+        t = timed(lambda: er(page))
+        result["pages_per_s_" + name] = {"median": round(1e3 / t["median_ms"], 2), "ms": t, "selected_tiles": er.last_stats["selected"]}
+    print(json.dumps(result))
+    return result
+
+
+if __name__ == "__main__":
+    main()
