@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 6
+#define TSII_ABI_VERSION 7
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -567,6 +567,51 @@ int tsii_page_tiles_fill(const uint8_t* page, const uint8_t* text, int h, int w,
  * The four byte planes are 4-byte aligned. */
 int tsii_compose_page_u8(const uint8_t* page, const uint8_t* text, const float* out, const int* slot, int n_sel,
                          int h, int w, int tile, int halo, uint8_t* clean, uint8_t* mask_u8, void* stream);
+
+/* ---- K9: validation metrics (csrc/metrics.hip).  The reference has none (it prints losses); these are this library's own. ---------
+ * Besides fp32 tensors: histograms are int32, sums and SSIM values are double.  No floating-point atomics: for the same inputs and
+ * shapes every output has the same bits on every run (integer counts meet with integer atomics, floating-point sums leave a block as
+ * one double and are added in a fixed order by a last kernel).
+ *
+ * Confusion histograms of a binary segmenter at k thresholds.  logits, target: fp32 [n, hw] (hw = H*W pixels per image, 1 <= hw < 2^31).
+ * A pixel is TEXT (class 1) where target > 0.5f, background (class 0) otherwise (NaN: background).  thresholds: k floats in HOST memory,
+ * 1 <= k <= 32, ascending (equal neighbours allowed, NaN refused); they are read during the call and travel as kernel arguments, the
+ * array may be reused as soon as the call returns.  They are LOGIT thresholds: log(p / (1 - p)) for a probability p.
+ *   hist[i, c, b], int32 [n, 2, k + 1] = number of pixels of image i and class c whose logit exceeds exactly b of the thresholds,
+ * with "exceeds" = the fp32 comparison logit > thresholds[j] -- the test tsii_tiles_text_mask applies; NaN exceeds nothing, +inf every
+ * finite threshold.  The k + 1 bins of an image's two classes sum to hw.  hist is CLEARED BY THE CALL ITSELF (the caller accumulates).
+ * At threshold j:  TP = sum_{b > j} hist[i,1,b],  FN = sum_{b <= j} hist[i,1,b],  FP = sum_{b > j} hist[i,0,b],  TN = sum_{b <= j} hist[i,0,b]. */
+int tsii_seg_confusion(const float* logits, const float* target, int n, int64_t hw, const float* thresholds, int k,
+                       int* hist, void* stream);
+
+/* Error sums of an inpainting result.  out, clean: fp32 NHWC [n,h,w,c] (h*w*c < 2^31).  mask: fp32, [n,h,w,c] (mask_is_plane == 0) or
+ * one plane [n,h,w] shared by the channels (mask_is_plane != 0); an ELEMENT (pixel, channel) is VALID where its mask value > 0.5f and
+ * a HOLE otherwise (the data set's convention: 1 = keep, 0 = hole).  With clamp01 != 0, o = fminf(fmaxf(out, 0), 1), else o = out.
+ *   d = o - clean                     one fp32 subtraction; |d| and d*d and all sums below in double
+ *   sums[i,0] = number of hole elements of image i (a plane mask counts a hole pixel c times)
+ *   sums[i,1] = sum |d| over hole elements     sums[i,2] = sum d*d over hole elements
+ *   sums[i,3] = sum |d| over valid elements    sums[i,4] = sum d*d over valid elements            sums: double [n,5], 8-byte aligned
+ * ws: tsii_inpaint_errors_ws_bytes(n,h,w,c) bytes, 8-byte aligned.  16-byte loads are used when h*w % 4 == 0, c <= 4 and the three
+ * tensors are 16-byte aligned; every other case takes an element-wise form with the same results up to the order of the double sums. */
+size_t tsii_inpaint_errors_ws_bytes(int n, int h, int w, int c);
+int tsii_inpaint_errors(const float* out, const float* clean, const float* mask, int mask_is_plane, int clamp01,
+                        int n, int h, int w, int c, double* sums, void* ws, size_t ws_bytes, void* stream);
+
+/* Mean structural similarity (Wang, Bovik, Sheikh, Simoncelli 2004) per image.  a, b: fp32 NHWC [n,h,w,c], 1 <= c <= 4, h, w >= 11
+ * (smaller is refused).  L = data_range > 0, C1 = (0.01 L)^2, C2 = (0.03 L)^2.
+ *   g[i] = exp(-(i - 5)^2 / (2 * 1.5^2)) / sum_j exp(-(j - 5)^2 / (2 * 1.5^2)),  i = 0..10     (sigma 1.5, the 11 weights sum to 1)
+ *   for every window position (y, x), 0 <= y <= h - 11, 0 <= x <= w - 11 (windows wholly inside the image) and every channel k:
+ *     E[f]  = sum_{i,j} g[i] g[j] f(y + i, x + j, k)
+ *     mu_a = E[a], mu_b = E[b], var_a = E[a a] - mu_a^2, var_b = E[b b] - mu_b^2, cov = E[a b] - mu_a mu_b     (population moments)
+ *     S = ((2 mu_a mu_b + C1) (2 cov + C2)) / ((mu_a^2 + mu_b^2 + C1) (var_a + var_b + C2))
+ *   ssim[i] = mean of S over the (h - 10) (w - 10) positions and the c channels of image i                    double [n], 8-byte aligned
+ * The weighted sums are fp32 (fmaf, horizontal pass then vertical pass, weights rounded to fp32), taken of the pixel values minus one
+ * reference pixel per 32 x 16 tile and channel (variance and covariance do not depend on it; the means get it back in double), S and its
+ * sum are double.  Exactly symmetric in (a, b); ssim(a, a) = 1 exactly.  ws: tsii_ssim_ws_bytes(n,h,w,c) bytes (0: shape refused),
+ * 8-byte aligned.  A masked form is not offered: compose first (tsii_compose_fwd). */
+size_t tsii_ssim_ws_bytes(int n, int h, int w, int c);
+int tsii_ssim(const float* a, const float* b, int n, int h, int w, int c, float data_range, double* ssim, void* ws,
+              size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

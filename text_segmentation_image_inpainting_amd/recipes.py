@@ -55,6 +55,12 @@ class InpaintingRecipe(_Recipe):
         self._batch = (corrupted, mask, clean)
         return self.trainer.step(corrupted, mask, None)
 
+    def evaluate(self, batches, metrics=None):
+        """Validation pass over ``(corrupted, mask, clean)`` batches: ``metrics.evaluate_inpainting`` on the model being trained
+        (``eval()`` for the call, no gradients, running statistics and optimizer state untouched)."""
+        from .metrics import evaluate_inpainting
+        return evaluate_inpainting(self.trainer.model, batches, metrics)
+
 
 class _SegAdapter(nn.Module):
     def __init__(self, net):
@@ -103,3 +109,9 @@ class SegmentationRecipe(_Recipe):
     def step(self, image, target):
         self.scheduler.batch_step()
         return self.trainer.step(image, None, target)
+
+    def evaluate(self, batches, thresholds=(0.5,)):
+        """Validation pass over ``(image, target)`` batches: ``metrics.evaluate_segmentation`` on the net being trained at the
+        given probability thresholds (an int ``n``: ``n`` evenly spaced ones)."""
+        from .metrics import SegmentationMetrics, evaluate_segmentation
+        return evaluate_segmentation(self.net, batches, SegmentationMetrics(thresholds))
