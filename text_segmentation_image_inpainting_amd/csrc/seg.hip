@@ -369,8 +369,11 @@ __global__ void bce_focal_bwd_kernel(const float* __restrict__ x, const float* _
         const float sgn = tv * 2.f - 1.f;
         const float u = -xv * sgn;
         const float pt = (u < 0.f ? u : 0.f) - softplus_neg_abs(u);
-        const float sig_u = 1.f / (1.f + expf(-u));
-        const float dpt = -sgn * (1.f - sig_u);
+        // 1 - sigmoid(u) from e = exp(-|u|), never as a difference from 1: at u = 7 the difference has lost three digits, and
+        // gamma * bce multiplies what is left (tests/test_small_kernels.py: test_bce_focal_fwd_bwd)
+        const float eu = expf(-fabsf(u));
+        const float one_minus_sig_u = (u > 0.f ? eu : 1.f) / (1.f + eu);
+        const float dpt = -sgn * one_minus_sig_u;
         const float bce = w * ((xv > 0.f ? xv : 0.f) - xv * tv + softplus_neg_abs(xv));
         const float dbce = w * (1.f / (1.f + expf(-xv)) - tv);
         dx[i] = gs * expf(pt * gamma) * (gamma * dpt * bce + dbce);
@@ -496,7 +499,7 @@ extern "C" int tsii_bce_focal_fwd(const float* x, const float* t, int64_t numel,
     TSII_REQUIRE(ws_bytes >= tsii_l1_ws_bytes(numel), "bce_focal_fwd: workspace too small");
     hipStream_t st = (hipStream_t)stream;
     int64_t nb = cdiv64(numel, 256);
-    if (nb > 1024) nb = 1024;
+    if (nb > REDUCE_BLOCKS) nb = REDUCE_BLOCKS;
     hipLaunchKernelGGL(bce_focal_partial_kernel, dim3((unsigned)nb), dim3(256), 0, st, x, t, numel, gamma, background_w, words_w, (float*)ws);
     int rc = check_launch("bce_focal_partial");
     if (rc) return rc;

@@ -17,6 +17,10 @@ static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }
 
+// Blocks (of 256 threads) of every *_partial_kernel that leaves one fp32 partial per block in a workspace of tsii_l1_ws_bytes():
+// the launch cap of loss.hip and seg.hip and the size of that workspace are this one number.
+static constexpr int REDUCE_BLOCKS = 1024;
+
 // Streaming kernels use a capped grid + grid-stride loop: 256 CUs x 8 blocks.
 static inline unsigned stream_grid(int64_t work_items, int block) {
     int64_t g = cdiv64(work_items, block);
