@@ -7,6 +7,8 @@ Needs an MI355X (the models have no CPU path).
     python examples/erase_text.py --synthetic            # seeded manga-like page, random-init weights
 
 Writes ``<name>_clean.png`` and ``<name>_mask.png`` (255 = text) per page; ``--synthetic`` also writes the page itself.
+``--min-area N`` drops the connected text regions of fewer than N pixels on the device before anything is inpainted; ``--boxes`` also
+writes ``<name>_boxes.png``, the page with the boxes of the kept regions outlined.
 """
 import argparse
 import os
@@ -47,6 +49,9 @@ def main(argv=None):
     ap.add_argument("--dilate", type=int, default=3)
     ap.add_argument("--threshold", type=float, default=0.5)
     ap.add_argument("--tile-batch", type=int, default=8)
+    ap.add_argument("--min-area", type=int, default=0, help="drop text regions of fewer pixels (after the dilation)")
+    ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
+    ap.add_argument("--boxes", action="store_true", help="also write <name>_boxes.png")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
@@ -58,7 +63,7 @@ def main(argv=None):
             net.load_state_dict(torch.load(ckpt, map_location="cpu"))      # the tolerant loader: reports and skips what does not fit
         nets.append(net.to(dev).eval())
     eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
-                          tile_batch=args.tile_batch)
+                          tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -69,13 +74,21 @@ def main(argv=None):
         out_folder = args.out_folder or args.img_folder
         os.makedirs(out_folder, exist_ok=True)
         names = sorted(f for f in os.listdir(args.img_folder) if f.lower().endswith(EXTENSIONS)
-                       and not f.endswith(("_clean.png", "_mask.png")))
+                       and not f.endswith(("_clean.png", "_mask.png", "_boxes.png")))
         pages = ((os.path.splitext(f)[0], np.asarray(Image.open(os.path.join(args.img_folder, f)).convert("RGB"))) for f in names)
     t0 = time.time()
     for name, page in pages:
         clean, mask = eraser(page)
         Image.fromarray(clean).save(os.path.join(out_folder, name + "_clean.png"))
         Image.fromarray(mask).save(os.path.join(out_folder, name + "_mask.png"))
+        if args.boxes:
+            from PIL import ImageDraw
+            boxed = Image.fromarray(page)
+            draw = ImageDraw.Draw(boxed)
+            for _, _, y0, x0, y1, x1 in eraser.last_regions["table"].tolist():
+                draw.rectangle([x0, y0, x1 - 1, y1 - 1], outline=(255, 0, 0))
+            boxed.save(os.path.join(out_folder, name + "_boxes.png"))
+            print("%s: %d text regions, %d kept" % (name, eraser.last_regions["found"], eraser.last_regions["kept"]))
         st = eraser.last_stats
         print("%s: %d x %d, %d of %d tiles inpainted, text fraction %.4f" %
               (name, page.shape[0], page.shape[1], st["selected"], st["tiles"], float((mask > 0).mean())))

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 7
+#define TSII_ABI_VERSION 8
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -612,6 +612,29 @@ int tsii_inpaint_errors(const float* out, const float* clean, const float* mask,
 size_t tsii_ssim_ws_bytes(int n, int h, int w, int c);
 int tsii_ssim(const float* a, const float* b, int n, int h, int w, int c, float data_range, double* ssim, void* ws,
               size_t ws_bytes, void* stream);
+
+/* ---- K10: text regions (csrc/regions.hip) -- connected components of the K8 text plane, their areas and boxes, and a minimum-area
+ * filter applied on the device (the reference's demo does this on the host: Examples/demo_segmentation.py:17-25,43 labels the mask,
+ * drops the regions below an area threshold and marks the rest).  All integer: the same inputs give the same bits on every run.
+ * text: uint8 [h,w], READ AND THEN REWRITTEN IN PLACE; a pixel is foreground where its byte is non-zero.  A COMPONENT is a maximal set
+ * of foreground pixels connected through the 4- or 8-neighbourhood (connectivity = 4 or 8) inside the page.  Its LABEL is
+ * 1 + min(y*w + x) over its pixels, its AREA its pixel count, its BOX y0, x0 inclusive and y1, x1 exclusive.  A component is KEPT iff
+ * area >= min_area (min_area <= 1 keeps everything).
+ *   labels[p], int32 [h,w]   = the label of p's component if that component is kept, else 0
+ *   text[p]                  = labels[p] != 0 ? 1 : 0
+ *   n_regions, int32 [2]     = {components found, components kept}
+ *   table, int32 [max_regions, 6]: row r = {label, area, y0, x0, y1, x1} of the r-th kept component in ascending label order (raster
+ *     order of each region's first pixel).  Only the first min(kept, max_regions) rows are written, the rows behind them are not
+ *     touched; n_regions[1] is the true count, which is how a caller sees the truncation.  max_regions == 0 with table == NULL is allowed.
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the number of
+ *     KEPT text pixels in each tile core -- what tsii_tiles_text_mask writes, after the filter.
+ * No allocation, no host synchronisation, everything on the caller's stream.  ws: tsii_text_regions_ws_bytes(h, w, max_regions) bytes
+ * (0: geometry refused), 4-byte aligned; the call leaves nothing there a later call depends on and needs nothing cleared beforehand.
+ * Refused (non-zero return, tsii_last_error, nothing written): connectivity not 4 or 8; h or w < 1; h*w > 2^31 - 2; max_regions < 0
+ * (or > 0 without a table); a bad tile geometry while core_count != NULL. */
+size_t tsii_text_regions_ws_bytes(int h, int w, int max_regions);
+int tsii_text_regions(uint8_t* text, int h, int w, int connectivity, int min_area, int max_regions,
+                      int tile, int halo, int* core_count, int* labels, int* table, int* n_regions, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -6,25 +6,11 @@
 // Stores are plain (default cache policy), not non-temporal: every output is read next by another kernel (the nets' first layers,
 // the mask kernel, compose), and a whole page's tiles (63 MB at 1170 x 1654, tile 512 / halo 64) fit the 256 MB MALL -- a
 // non-temporal store would send the hand-off through HBM.
-#include "tsii_common.h"
+#include "page_grid.h"
 
 #include <string.h>
 
 namespace tsii {
-
-struct PageGrid {
-    int h, w, tile, halo, s, ty, tx;
-};
-static inline PageGrid make_grid(int h, int w, int tile, int halo) {
-    PageGrid g;
-    g.h = h; g.w = w; g.tile = tile; g.halo = halo; g.s = tile - 2 * halo;
-    g.ty = cdiv(h, g.s); g.tx = cdiv(w, g.s);
-    return g;
-}
-static inline bool grid_ok(int h, int w, int tile, int halo) {
-    return h > 0 && w > 0 && tile > 0 && tile % 32 == 0 && halo >= 0 && tile - 2 * halo > 0 &&
-           (int64_t)h * w < (1ll << 31) - 4 && (int64_t)cdiv(h, tile - 2 * halo) * cdiv(w, tile - 2 * halo) * tile * (tile / 4) < (1ll << 31);
-}
 
 // mirror reflection without repeating the edge (period 2 (n - 1)); n == 1 -> 0
 __device__ __forceinline__ int reflect(int v, int n) {

@@ -17,6 +17,7 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
+from .regions import _text_regions, check_region_args, unpack_regions
 
 
 class TileGrid(NamedTuple):
@@ -131,13 +132,21 @@ class TextEraser:
     the side of the square the text is grown by (odd, 1..31).  Tiles without text in their core skip the filler
     (``skip_blank_tiles=False`` sends all of them); selected tiles go to it in row-major order, ``tile_batch`` at a time.
 
+    ``min_area`` > 1 drops the connected text regions (``connectivity`` 4 or 8, measured after the dilation) of fewer pixels before
+    anything else sees the text plane: they select no tile, are not painted over and are not in the returned mask.  ``regions=True``
+    (or a ``min_area`` > 1) also leaves ``last_regions``: a dict of ``table`` (numpy int32 ``[n, 6]``: label, area, y0, x0, y1, x1 of
+    the kept regions, at most ``max_regions`` rows), ``found``, ``kept`` and ``truncated``, read back with the tile counts in the
+    page's one synchronisation; the int32 label plane stays on the device as ``last_labels``.  With the defaults none of this runs
+    and both stay ``None``.
+
     The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
     the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
     ``clean`` equals the page wherever ``mask`` is 0.
     """
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
-                 threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True):
+                 threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
+                 max_regions=4096):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -145,6 +154,9 @@ class TextEraser:
             raise ValueError(f"dilate {dilate} must be odd, 1..31")
         if int(tile_batch) < 1:
             raise ValueError("tile_batch >= 1")
+        check_region_args(connectivity, min_area, max_regions)
+        self.min_area, self.connectivity, self.max_regions = int(min_area), int(connectivity), int(max_regions)
+        self.regions = bool(regions) or self.min_area > 1
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -157,6 +169,8 @@ class TextEraser:
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
         self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page
+        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only)
+        self.last_labels = None                         # its int32 label plane, left on the device
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
     def _upload(self, page):
@@ -182,6 +196,11 @@ class TextEraser:
                     logits = torch.empty((g.count, g.tile, g.tile), dtype=torch.float32, device=self.device)
                 logits[b0:b0 + n].copy_(lb)             # bf16 logits (bf16 activation storage) are cast here, once
         return logits
+
+    def _regions(self, text, g):
+        """filter the text plane in place -> ONE device tensor [filtered core counts | found, kept | table]; the labels stay on the device"""
+        self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g)
+        return packed
 
     def _fill(self, page_d, text, g, selected):
         ids = torch.tensor(selected, dtype=torch.int32).to(self.device)
@@ -211,7 +230,12 @@ class TextEraser:
         with torch.no_grad(), _eval_mode(self.segmenter, self.filler):
             logits = self._segment(page_d, g)
             text, counts = _tiles_text_mask(logits, g, self.logit_threshold, self.dilate)
+            if self.regions:
+                counts = self._regions(text, g)
             counts_h = counts.cpu().numpy()             # the one synchronisation before the download
+            if self.regions:
+                counts_h, table, found, kept, truncated = unpack_regions(counts_h, g.count, self.max_regions)
+                self.last_regions = {"table": table, "found": found, "kept": kept, "truncated": truncated}
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
             out, slot = self._fill(page_d, text, g, selected) if (selected and any_text) else (None, None)

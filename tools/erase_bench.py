@@ -2,6 +2,7 @@
 """Times one page through TextEraser stage by stage (HIP events on the launch stream) and prints one JSON line.
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
+                                [--min-area N [--connectivity 8]] [--all-text]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -11,6 +12,10 @@ timed is the cost of the pipeline, not the quality of a net.  For comparison, in
 * the mask stage the way examples/demo_segmentation.py does it (download the logits, threshold and nine torch.maximum on the CPU);
 * a torch restatement of the tile, mask and compose stages on the device;
 * the whole page with and without tile selection (pages / s, host clock around synchronised calls).
+``--min-area N`` (N > 0) adds the ``regions`` stage (tsii_text_regions in place on the text plane, with the core counts) between the
+mask and the read-back, which then carries the counts, the region counts and the table in its one copy; and ``host_route``, the same
+labelling done the usual way: download the mask, scipy.ndimage.label + find_objects + bincount (reported as unavailable without
+scipy).  ``--all-text`` makes the whole page one component: the worst case for the aggregation of areas and boxes.
 """
 import argparse
 import json
@@ -55,9 +60,14 @@ def main(argv=None):
     ap.add_argument("--text-fraction", type=float, default=0.1)
     ap.add_argument("--repeats", type=int, default=10)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--min-area", type=int, default=0, help="> 0: time the regions stage with this filter")
+    ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
+    ap.add_argument("--max-regions", type=int, default=4096)
+    ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
+    from text_segmentation_image_inpainting_amd import regions as RG
     from text_segmentation_image_inpainting_amd.synthetic import manga_tile
     assert torch.cuda.is_available(), "erase_bench needs an MI355X"
     dev = torch.device("cuda:0")
@@ -66,11 +76,15 @@ def main(argv=None):
     h, w = args.size
     page = np.ascontiguousarray((manga_tile(max(h, w), np.random.default_rng(0)).transpose(1, 2, 0)[:h, :w] * 255).astype(np.uint8))
     g = P.tile_grid(h, w, args.tile, args.halo)
-    logits_fixed = blob_logits(g, args.text_fraction, 1, dev)
+    logits_fixed = blob_logits(g, 0.0 if args.all_text else args.text_fraction, 1, dev)
+    if args.all_text:
+        logits_fixed.fill_(4.0)
+    with_regions = args.min_area > 0
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
-                          skip_blank_tiles=select)
+                          skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
+                          max_regions=args.max_regions)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]
         return er
@@ -78,9 +92,12 @@ def main(argv=None):
 
     ev = lambda: torch.cuda.Event(enable_timing=True)
     stages = ["upload", "page_tiles_norm", "segmenter", "tiles_text_mask", "counts_d2h", "page_tiles_fill", "filler", "compose_page_u8", "download"]
+    if with_regions:
+        stages.append("regions")                            # timed with its own pair of events, between the mask and the read-back
 
     def one_page():
-        marks = [ev() for _ in range(len(stages) + 2)]
+        marks = [ev() for _ in range(11)]
+        reg0, reg1 = ev(), ev()
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
@@ -93,9 +110,18 @@ def main(argv=None):
                 seg(x[b:b + args.tile_batch])
             marks[3].record()
             text, counts = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)
+            if with_regions:
+                reg0.record()
+                _, counts = RG._text_regions(text, args.connectivity, args.min_area, args.max_regions, g)
+                reg1.record()
             marks[4].record()
-            counts_h = counts.cpu().numpy()
+            counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table)
             marks[5].record()
+            d2h_words = int(counts_h.size)
+            region_info = None
+            if with_regions:
+                counts_h, table, found, kept, truncated = RG.unpack_regions(counts_h, g.count, args.max_regions)
+                region_info = {"found": found, "kept": kept, "truncated": truncated}
             selected = [t for t in range(g.count) if counts_h[t] > 0]
             ids = torch.tensor(selected, dtype=torch.int32).to(dev)
             slot_h = np.full(g.count, -1, np.int32)
@@ -115,9 +141,12 @@ def main(argv=None):
             clean.cpu(), mask_u8.cpu()
             marks[9].record()
         torch.cuda.synchronize()
-        t = [marks[i].elapsed_time(marks[i + 1]) for i in range(len(stages))]
+        t = [marks[i].elapsed_time(marks[i + 1]) for i in range(9)]
         t[5] = marks[10].elapsed_time(marks[6])
-        return t, len(selected), int(counts_h.sum()), (page_d, text, out, slot, tiles)
+        if with_regions:
+            t[3] = marks[3].elapsed_time(reg0)
+            t.append(reg0.elapsed_time(reg1))
+        return t, len(selected), int(counts_h.sum()), (page_d, text, out, slot, tiles), d2h_words, region_info
 
     for _ in range(args.warmup):
         one_page()
@@ -130,6 +159,8 @@ def main(argv=None):
     npx, tpx = h * w, args.tile * args.tile
     bytes_ = {"page_tiles_norm": 3 * npx + 12 * g.count * tpx, "tiles_text_mask": 5 * npx,
               "page_tiles_fill": 4 * npx * n_sel / g.count + 16 * n_sel * tpx, "compose_page_u8": 8 * npx + 12 * n_text}
+    if with_regions:
+        bytes_["regions"] = 18 * npx        # local 1 + 4, measure 4, filter 4 + 4 + 1 ("text regions"); seams and statistics on top
 
     def timed(fn, sync=True):
         for _ in range(args.warmup):
@@ -179,6 +210,21 @@ def main(argv=None):
     def torch_compose():
         return torch.where(text[..., None] > 0, torch.floor(filled.clamp(0, 1) * 255 + 0.5).byte(), page_d), text * 255
 
+    host_route = None
+    if with_regions:
+        text0, _ = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)      # the plane before the filter
+        try:
+            from scipy import ndimage
+            structure = np.ones((3, 3), np.int32) if args.connectivity == 8 else None
+
+            def host_regions():
+                m = text0.cpu().numpy()
+                lab, n = ndimage.label(m, structure=structure)
+                return ndimage.find_objects(lab), np.bincount(lab.reshape(-1), minlength=n + 1)
+            host_route = timed(host_regions, sync=False)
+        except ImportError:
+            host_route = "not available: scipy is not installed"
+
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
         "seg_model": args.seg_model, "fill_model": args.fill_model, "tiles": g.count, "selected_tiles": n_sel,
@@ -187,6 +233,10 @@ def main(argv=None):
         "kernel_gb": {k: round(v / 1e9, 5) for k, v in bytes_.items()},
         "kernel_tb_per_s": {k: round(v / (med[k] * 1e-3) / 1e12, 3) for k, v in bytes_.items()},
         "kernels_share_of_nets": round(sum(med[k] for k in bytes_) / (med["segmenter"] + med["filler"]), 5),
+        "all_text": args.all_text, "min_area": args.min_area, "connectivity": args.connectivity,
+        # the stages that copy to the host before the download: still one, whatever it carries
+        "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
+        "regions": runs[0][5], "host_route": host_route,
         "demo_route_mask_stage": timed(demo_mask, sync=False),
         "torch_on_device": {"page_tiles_norm": timed(torch_norm), "tiles_text_mask": timed(torch_mask), "compose_page_u8": timed(torch_compose)},
     }
