@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 8
+#define TSII_ABI_VERSION 9
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -635,6 +635,43 @@ int tsii_ssim(const float* a, const float* b, int n, int h, int w, int c, float 
 size_t tsii_text_regions_ws_bytes(int h, int w, int max_regions);
 int tsii_text_regions(uint8_t* text, int h, int w, int connectivity, int min_area, int max_regions,
                       int tile, int halo, int* core_count, int* labels, int* table, int* n_regions, void* ws, void* stream);
+
+/* ---- K11: working resolution (csrc/resample.hip) -- the two resamplings around a segmenter that works at its own size, as the
+ * reference's only end-to-end program does (Dataloader.py:285-317: the page is brought to a working size with Pillow's bicubic filter,
+ * the net's mask goes back to the page through nn.Upsample(bilinear, align_corners=False) and "> 0").  Integer arithmetic on the device;
+ * the same inputs give the same bits on every run.
+ *
+ * Bicubic resize of a uint8 page, byte for byte PIL.Image.resize((ws, hs), Image.BICUBIC) of an RGB image.  Per axis, from the input
+ * size `in` and the output size `out` (refused unless in, out >= 1 and in <= 8 out and out <= 8 in: a row then has at most 33 taps):
+ *   scale = in / out, fs = max(scale, 1.0), support = 2.0 * fs, taps = 2 * (int)ceil(support) + 1              (double precision)
+ *   for the output index xx: center = (xx + 0.5) * scale, xmin = max(0, (int)(center - support + 0.5)),
+ *     xmax = min(in, (int)(center + support + 0.5)), n = xmax - xmin
+ *   w[x] = bicubic((x + xmin - center + 0.5) / fs), x = 0..n-1, with a = -0.5:
+ *     ((a + 2)|t| - (a + 3)) t^2 + 1 for |t| < 1,   (((|t| - 5)|t| + 8)|t| - 4) a for |t| < 2,   0 otherwise
+ *   w is divided by its sum (accumulated in index order); k[x] = (int)(w[x] * 2^22 + 0.5), or (int)(w[x] * 2^22 - 0.5) for w[x] < 0
+ *   out[xx] = clip8((2^21 + sum_x k[x] * in[xmin + x]) >> 22)            int32 accumulation, arithmetic shift, clip8 = clamp to 0..255
+ * The horizontal pass runs first, to a uint8 intermediate, then the vertical pass; a pass with in == out is skipped.
+ * tsii_resize_taps: the row length of the table for (in, out); 0 = refused.
+ * tsii_resize_coeffs_u8: a plain HOST function (no device work, no stream): fills the host arrays bounds int32 [out, 2] = {xmin, n}
+ * and kk int32 [out, taps] (entries behind n are 0), in double precision with floating-point contraction off.
+ * tsii_page_resize_u8: page uint8 [h,w,3] -> out uint8 [hs,ws,3]; the four tables are DEVICE copies of what tsii_resize_coeffs_u8
+ * made for (h, hs) and (w, ws), taps_y / taps_x their row lengths (checked); the tables of a skipped pass may be NULL.  No
+ * workspace, no allocation, the caller's stream.  Bounds read from a table are clamped to the buffers before use. */
+int tsii_resize_taps(int in, int out);
+int tsii_resize_coeffs_u8(int in, int out, int* bounds, int* kk);
+int tsii_page_resize_u8(const uint8_t* page, int h, int w, int hs, int ws, const int* bounds_y, const int* kk_y,
+                        const int* bounds_x, const int* kk_x, int taps_y, int taps_x, uint8_t* out, void* stream);
+
+/* Working-resolution text plane onto the page: text_s uint8 [hs,ws] (non-zero = text; what tsii_tiles_text_mask leaves for the working
+ * page's own tile grid) -> text uint8 [h,w] of 0 / 1 and core_count int32 [ty*tx] on the PAGE's K8 tile geometry (cleared by the call;
+ * integer atomics), the convention of tsii_tiles_text_mask: selection, tsii_text_regions, fill and compose run unchanged behind it.
+ * "Bilinear, align_corners = False, then > 0" in integers.  Per axis, for the destination index d, source size in, destination size out:
+ *   num = max(0, (2 d + 1) * in - out),  i0 = num / (2 out),  frac = num % (2 out),  i1 = frac ? min(i0 + 1, in - 1) : i0
+ * and a page pixel is text iff any of its up to four taps (y0 | y1, x0 | x1) is.  This equals torch's interpolate(...) > 0 wherever no
+ * tap has a weight of exactly zero (there the float32 rounding of the weight decides in torch; here the tap does not count).
+ * Refused: a bad tile geometry; hs or ws < 1; (2 h + 1) * hs or (2 w + 1) * ws >= 2^31. */
+int tsii_text_plane_up(const uint8_t* text_s, int hs, int ws, int h, int w, int tile, int halo,
+                       uint8_t* text, int* core_count, void* stream);
 
 #ifdef __cplusplus
 }

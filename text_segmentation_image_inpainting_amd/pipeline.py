@@ -5,6 +5,11 @@ into a dilated text plane, sends only the tiles that contain text through an inp
 into the page bytes.  The page is uploaded once as uint8 and downloaded once as uint8; everything between stays on the device, in
 the four kernels of ``csrc/pipeline.hip`` (semantics: ``include/tsii_hip.h``, "K8: page pipeline") and the two nets.  Inference
 only: nothing here records autograd.
+
+With ``seg_long_side`` the segmenter works at its own resolution, as the reference's ``EvaluateSet`` has it: the page is resized on
+the device with Pillow's bicubic filter, byte for byte, and the working-resolution text plane comes back onto the page's grid with
+"bilinear, then ``> 0``" in integers (``csrc/resample.hip``; "K11: working resolution").  The inpainting net always sees the page's
+own pixels.
 """
 from contextlib import contextmanager
 from typing import NamedTuple
@@ -98,6 +103,75 @@ def _compose_page_u8(page, text, out, slot, g: TileGrid, clean, mask_u8):
          _lib.stream())
 
 
+def working_size(h, w, long_side):
+    """``(hs, ws)``: the size ``EvaluateSet(resize=long_side)`` resizes an ``h x w`` page to before it pads (Dataloader.py:285-317):
+    ``int(side * (long_side / max(h, w))) // 8 * 8`` per side -- and at least 8, where the reference would ask Pillow for an empty image."""
+    ratio = int(long_side) / max(int(h), int(w))
+    return tuple(max(8, int(x * ratio) // 8 * 8) for x in (int(h), int(w)))
+
+
+RESIZE_MAX_RATIO = 8            # per axis, either way: what tsii_page_resize_u8 accepts (a table row of at most 33 taps)
+_RESIZE_TABLES = {}             # (in, out, device) -> (bounds [out, 2], kk [out, taps], taps) on the device
+
+
+def _check_resize(h, w, hs, ws):
+    for a, b in ((h, hs), (w, ws)):
+        if a < 1 or b < 1 or a > RESIZE_MAX_RATIO * b or b > RESIZE_MAX_RATIO * a:
+            raise ValueError(f"resize {h} x {w} -> {hs} x {ws}: every side >= 1 and within {RESIZE_MAX_RATIO} x of its counterpart")
+
+
+def _resize_tables(n_in, n_out, device):
+    """device copies of ``tsii_resize_coeffs_u8``'s tables for one axis, made once per (in, out) pair and device"""
+    key = (int(n_in), int(n_out), str(device))
+    hit = _RESIZE_TABLES.get(key)
+    if hit is None:
+        taps = int(_lib.lib().tsii_resize_taps(key[0], key[1]))
+        if taps == 0:
+            raise ValueError(f"resize {n_in} -> {n_out} is out of range")
+        bounds, kk = np.zeros((key[1], 2), np.int32), np.zeros((key[1], taps), np.int32)
+        call("tsii_resize_coeffs_u8", key[0], key[1], bounds.ctypes.data, kk.ctypes.data)      # a host function: host arrays
+        hit = _RESIZE_TABLES[key] = (torch.from_numpy(bounds).to(device), torch.from_numpy(kk).to(device), taps)
+    return hit
+
+
+def _page_resize_u8(page, hs, ws):
+    """device page ``[H, W, 3]`` uint8 -> ``[hs, ws, 3]`` uint8 (``tsii_page_resize_u8``)"""
+    h, w = int(page.shape[0]), int(page.shape[1])
+    _check_resize(h, w, hs, ws)
+    by, ky, ty = _resize_tables(h, hs, page.device) if h != hs else (None, None, 0)
+    bx, kx, tx = _resize_tables(w, ws, page.device) if w != ws else (None, None, 0)
+    out = torch.empty((hs, ws, 3), dtype=torch.uint8, device=page.device)
+    _same_device(page, out, *[t for t in (by, ky, bx, kx) if t is not None])
+    call("tsii_page_resize_u8", ptr(page), h, w, int(hs), int(ws), ptr(by), ptr(ky), ptr(bx), ptr(kx), ty, tx, ptr(out), _lib.stream())
+    return out
+
+
+def resize_page_u8(page_u8, size, device=None):
+    """``[H, W, 3]`` uint8 -> ``[hs, ws, 3]`` uint8 for ``size = (hs, ws)``, equal byte for byte to
+    ``PIL.Image.resize((ws, hs), Image.BICUBIC)``, computed on the device.  numpy or torch in, the same kind (and device) out; a host
+    page is computed on ``device`` (default ``cuda:0``).  A side may change by a factor of 8 at the most, either way."""
+    t = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"page must be [H, W, 3] uint8, got {tuple(t.shape)} {t.dtype}")
+    hs, ws = int(size[0]), int(size[1])
+    _check_resize(int(t.shape[0]), int(t.shape[1]), hs, ws)
+    dev = torch.device(device) if device is not None else (t.device if t.is_cuda else torch.device("cuda:0"))
+    out = _page_resize_u8(t.to(dev).contiguous(), hs, ws)
+    if isinstance(page_u8, np.ndarray):
+        return out.cpu().numpy()
+    return out if out.device == page_u8.device else out.to(page_u8.device)
+
+
+def _text_plane_up(text_s, g: TileGrid):
+    """working-resolution text plane -> (text ``[g.h, g.w]`` of 0 / 1, core counts) on the page's grid ``g`` (``tsii_text_plane_up``)"""
+    text = torch.empty((g.h, g.w), dtype=torch.uint8, device=text_s.device)
+    counts = torch.empty((g.count,), dtype=torch.int32, device=text_s.device)
+    _same_device(text_s, text, counts)
+    call("tsii_text_plane_up", ptr(text_s), int(text_s.shape[0]), int(text_s.shape[1]), g.h, g.w, g.tile, g.halo, ptr(text), ptr(counts),
+         _lib.stream())
+    return text, counts
+
+
 def logit_of(threshold) -> float:
     """float32 ``log(p / (1 - p))``: the logit threshold ``TextEraser`` hands to ``tsii_tiles_text_mask`` (0 at p = 0.5)."""
     return float(np.log(np.float32(threshold) / (np.float32(1.0) - np.float32(threshold)), dtype=np.float32))
@@ -139,6 +213,13 @@ class TextEraser:
     page's one synchronisation; the int32 label plane stays on the device as ``last_labels``.  With the defaults none of this runs
     and both stay ``None``.
 
+    ``seg_long_side`` (a positive multiple of 8, like ``EvaluateSet.resize``): the segmenter sees the page resized to
+    ``working_size(H, W, seg_long_side)`` -- long side ``seg_long_side``, both sides floored to a multiple of 8, Pillow's bicubic
+    filter -- on that page's own tile grid; ``threshold`` and ``dilate`` act at that resolution, as in the reference, and the text
+    plane is brought back to the page ("bilinear, then ``> 0``") before anything else sees it: ``min_area``, the returned mask and
+    the filler work in page pixels.  A side of the page may be at most 8 x its working side (and the other way round).
+    ``last_stats`` then also has ``seg_tiles`` and ``seg_size``.  ``None`` (the default): the page's own resolution, none of this runs.
+
     The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
     the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
     ``clean`` equals the page wherever ``mask`` is 0.
@@ -146,7 +227,7 @@ class TextEraser:
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
-                 max_regions=4096):
+                 max_regions=4096, seg_long_side=None):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -155,6 +236,9 @@ class TextEraser:
         if int(tile_batch) < 1:
             raise ValueError("tile_batch >= 1")
         check_region_args(connectivity, min_area, max_regions)
+        if seg_long_side is not None and (int(seg_long_side) != seg_long_side or seg_long_side < 8 or seg_long_side % 8):
+            raise ValueError(f"seg_long_side {seg_long_side} must be a positive multiple of 8")
+        self.seg_long_side = None if seg_long_side is None else int(seg_long_side)
         self.min_area, self.connectivity, self.max_regions = int(min_area), int(connectivity), int(max_regions)
         self.regions = bool(regions) or self.min_area > 1
         self.segmenter, self.filler = segmenter, filler
@@ -168,7 +252,7 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size")
         self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only)
         self.last_labels = None                         # its int32 label plane, left on the device
 
@@ -226,10 +310,17 @@ class TextEraser:
     def _erase(self, page):
         page_d = self._upload(page)
         h, w = int(page_d.shape[0]), int(page_d.shape[1])
-        g = tile_grid(h, w, self.tile, self.halo)
+        g = gs = tile_grid(h, w, self.tile, self.halo)  # gs: the grid the segmenter works on
+        if self.seg_long_side is not None:
+            hs, ws = working_size(h, w, self.seg_long_side)
+            _check_resize(h, w, hs, ws)
+            if (hs, ws) != (h, w):
+                gs = tile_grid(hs, ws, self.tile, self.halo)
         with torch.no_grad(), _eval_mode(self.segmenter, self.filler):
-            logits = self._segment(page_d, g)
-            text, counts = _tiles_text_mask(logits, g, self.logit_threshold, self.dilate)
+            logits = self._segment(page_d if gs is g else _page_resize_u8(page_d, gs.h, gs.w), gs)
+            text, counts = _tiles_text_mask(logits, gs, self.logit_threshold, self.dilate)
+            if gs is not g:
+                text, counts = _text_plane_up(text, g)
             if self.regions:
                 counts = self._regions(text, g)
             counts_h = counts.cpu().numpy()             # the one synchronisation before the download
@@ -244,6 +335,8 @@ class TextEraser:
             clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
             _compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
         self.last_stats = {"tiles": g.count, "selected": len(selected) if out is not None else 0, "text_pixels": int(counts_h.sum())}
+        if self.seg_long_side is not None:
+            self.last_stats.update(seg_tiles=gs.count, seg_size=(gs.h, gs.w))
         if isinstance(page, np.ndarray):
             both_h = both.cpu().numpy()
             return both_h[:h * w * 3].reshape(h, w, 3), both_h[off:].reshape(h, w)

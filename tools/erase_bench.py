@@ -2,7 +2,7 @@
 """Times one page through TextEraser stage by stage (HIP events on the launch stream) and prints one JSON line.
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
-                                [--min-area N [--connectivity 8]] [--all-text]
+                                [--min-area N [--connectivity 8]] [--all-text] [--seg-long-side N]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -16,6 +16,10 @@ timed is the cost of the pipeline, not the quality of a net.  For comparison, in
 mask and the read-back, which then carries the counts, the region counts and the table in its one copy; and ``host_route``, the same
 labelling done the usual way: download the mask, scipy.ndimage.label + find_objects + bincount (reported as unavailable without
 scipy).  ``--all-text`` makes the whole page one component: the worst case for the aggregation of areas and boxes.
+``--seg-long-side N`` runs the segmenter at the working size ``working_size(H, W, N)`` and adds the stages ``resize``
+(tsii_page_resize_u8, between the upload and the tiles) and ``plane_up`` (tsii_text_plane_up, behind the mask); the synthetic text is
+the same blob field, sampled at the working size.  ``host_route_resample`` times the same two steps the way the reference does them:
+download the page, ``PIL.Image.resize(BICUBIC)``, upload; download the working mask, ``interpolate(bilinear) > 0``, upload.
 """
 import argparse
 import json
@@ -32,16 +36,21 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 
-def blob_logits(g, fraction, seed, dev):
-    """per-tile logits [nt, T, T] of a page whose text is rectangular blobs covering about ``fraction`` of it"""
+def blob_field(h, w, fraction, seed):
+    """logits [h, w] of a page whose text is rectangular blobs covering about ``fraction`` of it"""
     rng = np.random.default_rng(seed)
-    page = np.full((g.h, g.w), -4.0, np.float32)
-    target, covered = fraction * g.h * g.w, 0
+    page = np.full((h, w), -4.0, np.float32)
+    target, covered = fraction * h * w, 0
     while covered < target:
         bh, bw = int(rng.integers(30, 120)), int(rng.integers(60, 300))
-        y, x = int(rng.integers(0, max(1, g.h - bh))), int(rng.integers(0, max(1, g.w - bw)))
+        y, x = int(rng.integers(0, max(1, h - bh))), int(rng.integers(0, max(1, w - bw)))
         page[y:y + bh, x:x + bw] = 4.0
         covered += bh * bw
+    return page
+
+
+def tile_logits(page, g, dev):
+    """per-tile logits [nt, T, T] of the logit field ``page`` on the grid ``g``"""
     ext = np.pad(page, ((g.halo, g.ty * g.stride + g.halo), (g.halo, g.tx * g.stride + g.halo)), mode="edge")
     tiles = np.stack([ext[i * g.stride:i * g.stride + g.tile, j * g.stride:j * g.stride + g.tile]
                       for i in range(g.ty) for j in range(g.tx)])
@@ -64,6 +73,7 @@ def main(argv=None):
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
     ap.add_argument("--max-regions", type=int, default=4096)
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
+    ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
@@ -75,18 +85,25 @@ def main(argv=None):
     seg, fil = getattr(T, args.seg_model)().to(dev).eval(), getattr(T, args.fill_model)().to(dev).eval()
     h, w = args.size
     page = np.ascontiguousarray((manga_tile(max(h, w), np.random.default_rng(0)).transpose(1, 2, 0)[:h, :w] * 255).astype(np.uint8))
-    g = P.tile_grid(h, w, args.tile, args.halo)
-    logits_fixed = blob_logits(g, 0.0 if args.all_text else args.text_fraction, 1, dev)
+    g = gs = P.tile_grid(h, w, args.tile, args.halo)      # gs: the segmenter's grid
+    hs, ws = (h, w) if args.seg_long_side is None else P.working_size(h, w, args.seg_long_side)
+    if (hs, ws) != (h, w):
+        gs = P.tile_grid(hs, ws, args.tile, args.halo)
+    with_seg = gs is not g
+    field = blob_field(h, w, 0.0 if args.all_text else args.text_fraction, 1)
     if args.all_text:
-        logits_fixed.fill_(4.0)
+        field.fill(4.0)
+    if with_seg:                                          # the same text, sampled at the working size
+        field = F.interpolate(torch.from_numpy(field)[None, None], size=(hs, ws), mode="nearest")[0, 0].numpy()
+    logits_fixed = tile_logits(field, gs, dev)
     with_regions = args.min_area > 0
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
-                          max_regions=args.max_regions)
+                          max_regions=args.max_regions, seg_long_side=args.seg_long_side)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
-        er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]
+        er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
     eraser = make(True)
 
@@ -94,22 +111,33 @@ def main(argv=None):
     stages = ["upload", "page_tiles_norm", "segmenter", "tiles_text_mask", "counts_d2h", "page_tiles_fill", "filler", "compose_page_u8", "download"]
     if with_regions:
         stages.append("regions")                            # timed with its own pair of events, between the mask and the read-back
+    if with_seg:
+        stages += ["resize", "plane_up"]                    # their own pairs of events: behind the upload / behind the mask
 
     def one_page():
         marks = [ev() for _ in range(11)]
-        reg0, reg1 = ev(), ev()
+        reg0, reg1, res1, up0, up1 = ev(), ev(), ev(), ev(), ev()
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
             page_d = page_pinned.to(dev)
             marks[1].record()
-            tiles = P._page_tiles_norm(page_d, g, eraser.scale, eraser.shift)
+            seg_page = page_d
+            if with_seg:
+                seg_page = P._page_resize_u8(page_d, hs, ws)
+                res1.record()
+            tiles = P._page_tiles_norm(seg_page, gs, eraser.scale, eraser.shift)
             marks[2].record()
             x = tiles.permute(0, 3, 1, 2)
-            for b in range(0, g.count, args.tile_batch):
+            for b in range(0, gs.count, args.tile_batch):
                 seg(x[b:b + args.tile_batch])
             marks[3].record()
-            text, counts = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)
+            text, counts = P._tiles_text_mask(logits_fixed, gs, eraser.logit_threshold, args.dilate)
+            text_s = text
+            if with_seg:
+                up0.record()
+                text, counts = P._text_plane_up(text, g)
+                up1.record()
             if with_regions:
                 reg0.record()
                 _, counts = RG._text_regions(text, args.connectivity, args.min_area, args.max_regions, g)
@@ -146,7 +174,11 @@ def main(argv=None):
         if with_regions:
             t[3] = marks[3].elapsed_time(reg0)
             t.append(reg0.elapsed_time(reg1))
-        return t, len(selected), int(counts_h.sum()), (page_d, text, out, slot, tiles), d2h_words, region_info
+        if with_seg:
+            t[1] = res1.elapsed_time(marks[2])
+            t[3] = marks[3].elapsed_time(up0)
+            t += [marks[1].elapsed_time(res1), up0.elapsed_time(up1)]
+        return t, len(selected), int(counts_h.sum()), (page_d, text, out, slot, tiles, text_s), d2h_words, region_info
 
     for _ in range(args.warmup):
         one_page()
@@ -157,8 +189,11 @@ def main(argv=None):
 
     # bytes each kernel has to move ("page pipeline")
     npx, tpx = h * w, args.tile * args.tile
-    bytes_ = {"page_tiles_norm": 3 * npx + 12 * g.count * tpx, "tiles_text_mask": 5 * npx,
+    nsp = hs * ws
+    bytes_ = {"page_tiles_norm": 3 * nsp + 12 * gs.count * tpx, "tiles_text_mask": 5 * nsp,
               "page_tiles_fill": 4 * npx * n_sel / g.count + 16 * n_sel * tpx, "compose_page_u8": 8 * npx + 12 * n_text}
+    if with_seg:
+        bytes_.update(resize=3 * npx + 3 * nsp, plane_up=nsp + npx)      # DESIGN.md, "working resolution"
     if with_regions:
         bytes_["regions"] = 18 * npx        # local 1 + 4, measure 4, filter 4 + 4 + 1 ("text regions"); seams and statistics on top
 
@@ -175,7 +210,7 @@ def main(argv=None):
             vals.append((time.perf_counter() - t0) * 1e3)
         return {"median_ms": round(statistics.median(vals), 4), "min_ms": round(min(vals), 4), "max_ms": round(max(vals), 4)}
 
-    page_d, text, out, slot, tiles = keep
+    page_d, text, out, slot, tiles, text_s = keep
     # (a) the parent's route for the mask stage: the page's logits to the host, threshold + 3 x 3 max-pool with nine torch.maximum
     stitched = torch.randn(1, 1, h, w, device=dev)
 
@@ -210,6 +245,19 @@ def main(argv=None):
     def torch_compose():
         return torch.where(text[..., None] > 0, torch.floor(filled.clamp(0, 1) * 255 + 0.5).byte(), page_d), text * 255
 
+    host_resample = None
+    if with_seg:
+        from PIL import Image
+
+        def host_resize():
+            small = np.asarray(Image.fromarray(page_d.cpu().numpy()).resize((ws, hs), Image.BICUBIC))
+            return torch.from_numpy(small).to(dev)
+
+        def host_plane_up():
+            up = F.interpolate(text_s.cpu()[None, None].float(), size=(h, w), mode="bilinear", align_corners=False) > 0
+            return up[0, 0].to(torch.uint8).to(dev)
+        host_resample = {"resize": timed(host_resize), "plane_up": timed(host_plane_up)}
+
     host_route = None
     if with_regions:
         text0, _ = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)      # the plane before the filter
@@ -228,6 +276,7 @@ def main(argv=None):
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
         "seg_model": args.seg_model, "fill_model": args.fill_model, "tiles": g.count, "selected_tiles": n_sel,
+        "seg_long_side": args.seg_long_side, "seg_size": [hs, ws], "seg_tiles": gs.count, "host_route_resample": host_resample,
         "text_fraction": round(n_text / npx, 4), "repeats": args.repeats, "warmup": args.warmup,
         "stage_ms": {s: {"median": round(med[s], 4), "min": round(min(v), 4), "max": round(max(v), 4)} for s, v in ms.items()},
         "kernel_gb": {k: round(v / 1e9, 5) for k, v in bytes_.items()},
