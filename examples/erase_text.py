@@ -8,7 +8,8 @@ Needs an MI355X (the models have no CPU path).
 
 Writes ``<name>_clean.png`` and ``<name>_mask.png`` (255 = text) per page; ``--synthetic`` also writes the page itself.
 ``--min-area N`` drops the connected text regions of fewer than N pixels on the device before anything is inpainted; ``--boxes`` also
-writes ``<name>_boxes.png``, the page with the boxes of the kept regions outlined.
+writes ``<name>_boxes.png``, the page with the boxes of the kept regions outlined.  ``--hull`` fills the convex hull of every kept region
+into the mask on the device (the reference demo's ``cv2.convexHull`` step), so that the inpainting net gets one solid hole per text block.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 """
@@ -54,6 +55,7 @@ def main(argv=None):
     ap.add_argument("--min-area", type=int, default=0, help="drop text regions of fewer pixels (after the dilation)")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
     ap.add_argument("--boxes", action="store_true", help="also write <name>_boxes.png")
+    ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
@@ -67,7 +69,7 @@ def main(argv=None):
         nets.append(net.to(dev).eval())
     eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
-                          seg_long_side=args.seg_long_side)
+                          seg_long_side=args.seg_long_side, hull=args.hull)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 9
+#define TSII_ABI_VERSION 10
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -672,6 +672,38 @@ int tsii_page_resize_u8(const uint8_t* page, int h, int w, int hs, int ws, const
  * Refused: a bad tile geometry; hs or ws < 1; (2 h + 1) * hs or (2 w + 1) * ws >= 2^31. */
 int tsii_text_plane_up(const uint8_t* text_s, int hs, int ws, int h, int w, int tile, int halo,
                        uint8_t* text, int* core_count, void* stream);
+
+/* ---- K12: region hulls (csrc/hull.hip) -- the last step of the reference's demo (Examples/demo_segmentation.py: cv2.convexHull of every
+ * region that passed the area filter, drawn filled): the convex hull of every region in the table is filled into the text plane on the
+ * device, behind tsii_text_regions.  All integer, every product and cross product in int64: one defined answer, exact for every page
+ * tsii_text_regions accepts, the same bits on every run.
+ * Inputs as tsii_text_regions leaves them: text uint8 [h,w] (non-zero = text), labels int32 [h,w], table int32 [max_regions,6],
+ * n_regions int32 [2] ON THE DEVICE (the call does not read it on the host).  R = min(n_regions[1], max_regions) table rows are in use;
+ * for r < R, C_r is the set of pixels whose label is table[r][0], taken as integer points (y, x), and H_r the set of integer points of
+ * the page in the CLOSED convex hull of C_r (boundary points are in; collinear and single-pixel components give a segment or a point).
+ * Row form: a component meets every row of its box; with xmin_r(y), xmax_r(y) its leftmost and rightmost pixel in row y of [y0, y1),
+ * L_r the greatest convex function <= xmin_r and U_r the least concave function >= xmax_r on those rows, row y of H_r is the interval
+ * [ceil(L_r(y)), floor(U_r(y))]; between two neighbouring envelope vertices (ya, xa), (yb, xb) the envelope at row y is
+ * (xa (yb - y) + xb (y - ya)) / (yb - ya), rounded with exact integer ceiling (left side) or floor (right side).
+ *   text[p]                       = 1 iff text[p] != 0 on entry or p lies in some H_r, else 0.  Hulls may overlap one another, cover
+ *     background and cover regions the area filter dropped.  Kept regions beyond the table (kept > max_regions) keep their own pixels
+ *     and get no hull.
+ *   hull_area, int32 [max_regions]: hull_area[r] = |H_r| for r < R; the rows behind R are not touched.
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the number of text
+ *     pixels of the FINAL plane in each tile core (integer atomics: independent of block order).
+ *   labels, table and n_regions are read only.
+ * No allocation, no host synchronisation, everything on the caller's stream; no grid-wide barrier and no waiting on another block.
+ * ws: tsii_region_hulls_ws_bytes(h, w, max_regions) bytes (0: geometry refused), 4-byte aligned; it depends on (h, w, max_regions)
+ * only, needs nothing cleared beforehand and holds nothing a later call depends on.  (Distinct regions share no pixel and each has a
+ * run in every row of its box, so the (region, row) extents of all regions number at most min(max_regions * h, h * ceil(w / 2)); a
+ * prefix sum of the box heights over the table, on the device, gives every region its offset inside that bound.)
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1; h*w > 2^31 - 2; max_regions < 1; a NULL among text, labels,
+ * table, n_regions, hull_area, ws; a bad tile geometry while core_count != NULL.
+ * Every box or count read from table or n_regions is clamped to the page and to max_regions before use: a table that does not belong to
+ * the labels gives wrong bytes, never an access outside the buffers (the rule of tsii_page_resize_u8). */
+size_t tsii_region_hulls_ws_bytes(int h, int w, int max_regions);
+int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions, int max_regions,
+                      int tile, int halo, int* core_count, int* hull_area, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,364 @@
+// K12: region hulls (include/tsii_hip.h, "region hulls"): the convex hull of every region in the table tsii_text_regions left is filled
+// into the uint8 text plane, in place; its pixel count goes to hull_area and the per-tile core counts are taken again of the final
+// plane.  All integer, cross products in int64: one defined answer, the same bits on every run.
+//
+// A region meets every row of its box, so its hull is, row by row, the interval between the lower convex envelope of the rows'
+// leftmost pixels and the upper concave envelope of their rightmost ones.  A PAIR is one (region, row of its box); the pairs of all
+// table rows lie one region after the other in the workspace and a thread of the middle kernels owns one pair.
+//   1. offsets:  one block scans the box heights of the table rows (int64) -> every region's first pair; clears its hull_area;
+//   2. init:     xmin = INT_MAX, xmax = -1 for every pair in use (nothing in ws has to be cleared by the caller);
+//   3. extents:  one thread per pixel of the label plane; the first / last pixel of a row run finds its table row by binary search
+//                (the table ascends in label) and lowers xmin / raises xmax of its pair with one atomic;
+//   4. vertices: pair i of a region is a vertex of the lower envelope iff the largest slope from any earlier row to it is smaller than
+//                the smallest slope from it to any later row (cross-multiplied); the upper envelope likewise.  O(rows) per pair, all
+//                pairs in parallel: a page-tall region is spread over rows / 256 blocks instead of one dependent chain;
+//   5. fill:     max-scans over the vertex flags give every pair its neighbouring vertices on both envelopes (a region's first and last
+//                rows are vertices, so the scans never leave the region), the row formula gives [xl, xr], a wave per row stores the 1s;
+//   6. finish:   one pass over the plane: bytes to 0 / 1, text pixels per tile core.
+// No grid-wide barrier, no waiting on another block: each step is its own launch.  Everything read from the table or n_regions is
+// clamped before use: a table that does not belong to the labels gives wrong bytes, never an access outside the buffers.
+#include "page_grid.h"
+
+#include <limits.h>
+
+namespace tsii {
+
+#ifdef TSII_HIP_EMU
+// the test emulator runs one thread at a time and supplies atomicAdd only
+static inline int atomicMin(int* p, int v) { const int o = *p; if (v < o) *p = v; return o; }
+static inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v; return o; }
+#endif
+
+constexpr int HL_THREADS = 256;
+constexpr int HL_W = 64, HL_H = 32;              // rectangle of the finish kernel: a wave reads 64 consecutive bytes of a row
+constexpr int HL_HDR = 2;                        // ws[0] = pairs in use, ws[1] = R
+
+struct HullWs {
+    int64_t npairs;                              // the bound on the pairs, from (h, w, max_regions) alone
+    int* hdr;
+    int* roff;                                   // [max_regions] first pair of a region
+    int* rht;                                    // [max_regions] its rows (0: the region is skipped)
+    int* ext;                                    // [npairs][2] xmin, xmax
+    uint8_t* vflag;                              // [npairs] bit 0: vertex of the lower envelope, bit 1: of the upper one
+};
+static inline bool hull_geometry(int h, int w, int max_regions, int64_t* npairs) {
+    if (h < 1 || w < 1 || (int64_t)h * w > (1ll << 31) - 2 || max_regions < 1) return false;
+    const int64_t a = (int64_t)max_regions * h, b = (int64_t)h * cdiv(w, 2);
+    *npairs = a < b ? a : b;
+    return true;
+}
+static inline HullWs hull_ws(void* ws, int max_regions, int64_t npairs) {
+    HullWs r;
+    r.npairs = npairs;
+    r.hdr = static_cast<int*>(ws);
+    r.roff = r.hdr + HL_HDR;
+    r.rht = r.roff + max_regions;
+    r.ext = r.rht + max_regions;
+    r.vflag = reinterpret_cast<uint8_t*>(r.ext + 2 * npairs);
+    return r;
+}
+
+__device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// inclusive max-scan of one int per thread over the block; sh holds 2 * HL_THREADS ints
+__device__ __forceinline__ int block_max_scan(int v, int* sh, int tid) {
+    int cur = 0;
+    sh[tid] = v;
+    __syncthreads();
+    for (int d = 1; d < HL_THREADS; d <<= 1) {
+        const int a = sh[cur + tid], b = tid >= d ? sh[cur + tid - d] : INT_MIN;
+        cur ^= HL_THREADS;
+        sh[cur + tid] = a > b ? a : b;
+        __syncthreads();
+    }
+    const int r = sh[cur + tid];
+    __syncthreads();
+    return r;
+}
+
+// ---- 1. offsets ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(HL_THREADS) void hull_offsets_kernel(const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
+                                                                  int h, int64_t npairs, int* __restrict__ hdr, int* __restrict__ roff,
+                                                                  int* __restrict__ rht, int* __restrict__ hull_area) {
+    __shared__ long long sh[2 * HL_THREADS];
+    const int tid = threadIdx.x;
+    const int R = clampi(n_regions[1], 0, max_regions);
+    long long carry = 0;
+    for (int r0 = 0; r0 < R; r0 += HL_THREADS) {
+        const int r = r0 + tid;
+        int ht = 0;
+        if (r < R) {
+            const int y0 = clampi(table[(int64_t)r * 6 + 2], 0, h);
+            ht = clampi(table[(int64_t)r * 6 + 4], y0, h) - y0;
+        }
+        int cur = 0;
+        sh[tid] = ht;
+        __syncthreads();
+        for (int d = 1; d < HL_THREADS; d <<= 1) {
+            const long long t = sh[cur + tid] + (tid >= d ? sh[cur + tid - d] : 0);
+            cur ^= HL_THREADS;
+            sh[cur + tid] = t;
+            __syncthreads();
+        }
+        const long long first = carry + sh[cur + tid] - ht;
+        carry += sh[cur + HL_THREADS - 1];
+        __syncthreads();
+        if (r < R) {
+            roff[r] = (int)(first < npairs ? first : npairs);
+            rht[r] = first + ht <= npairs ? ht : 0;          // only a table that does not belong to the labels gets here with more
+            hull_area[r] = 0;
+        }
+    }
+    if (tid == 0) {
+        hdr[0] = (int)(carry < npairs ? carry : npairs);
+        hdr[1] = R;
+    }
+}
+
+// ---- 2. init ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(HL_THREADS) void hull_init_kernel(const int* __restrict__ hdr, int* __restrict__ ext) {
+    const int64_t q = (int64_t)blockIdx.x * HL_THREADS + threadIdx.x;
+    if (q >= hdr[0]) return;
+    ext[2 * q] = INT_MAX;
+    ext[2 * q + 1] = -1;
+}
+
+// ---- 3. extents ------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(HL_THREADS) void hull_extents_kernel(const int* __restrict__ labels, int h, int w, const int* __restrict__ table,
+                                                                  const int* __restrict__ hdr, const int* __restrict__ roff,
+                                                                  const int* __restrict__ rht, int* ext) {
+    const int64_t p = (int64_t)blockIdx.x * HL_THREADS + threadIdx.x;
+    if (p >= (int64_t)h * w) return;
+    const int lab = labels[p];
+    if (lab == 0) return;
+    const int y = (int)(p / w), x = (int)(p - (int64_t)y * w);
+    const bool first = x == 0 || labels[p - 1] != lab, last = x == w - 1 || labels[p + 1] != lab;
+    if (!first && !last) return;
+    const int R = hdr[1];
+    int lo = 0, hi = R;
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (table[(int64_t)mid * 6] < lab) lo = mid + 1; else hi = mid;
+    }
+    if (lo >= R || table[(int64_t)lo * 6] != lab) return;      // a kept region beyond the table: no hull
+    const int i = y - clampi(table[(int64_t)lo * 6 + 2], 0, h);
+    if (i < 0 || i >= rht[lo]) return;
+    int* e = ext + 2 * ((int64_t)roff[lo] + i);
+    if (first) atomicMin(e, x);
+    if (last) atomicMax(e + 1, x);
+}
+
+// the region and the row of pair q; false: q belongs to no region
+__device__ __forceinline__ bool pair_region(int q, int R, const int* __restrict__ roff, const int* __restrict__ rht, int* r, int* i, int* n) {
+    int lo = 0, hi = R;                                       // the last region that starts at or before q
+    while (lo < hi) {
+        const int mid = (lo + hi) >> 1;
+        if (roff[mid] <= q) lo = mid + 1; else hi = mid;
+    }
+    if (lo == 0) return false;
+    *r = lo - 1;
+    *i = q - roff[lo - 1];
+    *n = rht[lo - 1];
+    return *i < *n;
+}
+
+// ---- 4. vertices -----------------------------------------------------------------------------------------------------------------
+// slopes are fractions dx / dy with dy > 0, compared by cross-multiplication in int64
+__global__ __launch_bounds__(HL_THREADS) void hull_vertices_kernel(int w, const int* __restrict__ hdr, const int* __restrict__ roff,
+                                                                   const int* __restrict__ rht, const int* __restrict__ ext,
+                                                                   uint8_t* __restrict__ vflag) {
+    const int64_t q64 = (int64_t)blockIdx.x * HL_THREADS + threadIdx.x;
+    if (q64 >= hdr[0]) return;
+    const int q = (int)q64;
+    int r, i, n;
+    if (!pair_region(q, hdr[1], roff, rht, &r, &i, &n)) return;
+    int flags = 3;
+    if (i > 0 && i < n - 1) {
+        const int* e = ext + 2 * (int64_t)(q - i);
+        const int xl = clampi(e[2 * i], 0, w - 1), xr = clampi(e[2 * i + 1], 0, w - 1);
+        // over the earlier rows: the largest slope to xl, the smallest to xr; row i - 1 starts them
+        int64_t an = xl - clampi(e[2 * (i - 1)], 0, w - 1), ad = 1, bn = xr - clampi(e[2 * (i - 1) + 1], 0, w - 1), bd = 1;
+        for (int j = i - 2; j >= 0; --j) {
+            const int64_t d = i - j, nl = xl - clampi(e[2 * j], 0, w - 1), nr = xr - clampi(e[2 * j + 1], 0, w - 1);
+            if (nl * ad > an * d) { an = nl; ad = d; }
+            if (nr * bd < bn * d) { bn = nr; bd = d; }
+        }
+        // over the later rows: the smallest slope from xl, the largest from xr
+        int64_t cn = clampi(e[2 * (i + 1)], 0, w - 1) - xl, cd = 1, dn = clampi(e[2 * (i + 1) + 1], 0, w - 1) - xr, dd = 1;
+        for (int k = i + 2; k < n; ++k) {
+            const int64_t d = k - i, nl = clampi(e[2 * k], 0, w - 1) - xl, nr = clampi(e[2 * k + 1], 0, w - 1) - xr;
+            if (nl * cd < cn * d) { cn = nl; cd = d; }
+            if (nr * dd > dn * d) { dn = nr; dd = d; }
+        }
+        flags = (an * cd < cn * ad ? 1 : 0) | (bn * dd > dn * bd ? 2 : 0);
+    }
+    vflag[q] = (uint8_t)flags;
+}
+
+// ---- 5. intervals and fill -------------------------------------------------------------------------------------------------------
+// the envelope through (ya, xa), (yb, xb) at row y, ya < y < yb, all values >= 0: exact ceiling (up) or floor
+__device__ __forceinline__ int envelope_at(int64_t ya, int64_t xa, int64_t yb, int64_t xb, int64_t y, bool up) {
+    const int64_t den = yb - ya, num = xa * (yb - y) + xb * (y - ya) + (up ? den - 1 : 0);
+    if (((num | den) >> 32) == 0) return (int)((unsigned)num / (unsigned)den);     // every page tsii_text_regions accepts
+    return (int)(num / den);
+}
+
+__global__ __launch_bounds__(HL_THREADS) void hull_fill_kernel(uint8_t* text, int h, int w, const int* __restrict__ table,
+                                                               const int* __restrict__ hdr, const int* __restrict__ roff,
+                                                               const int* __restrict__ rht, const int* __restrict__ ext,
+                                                               const uint8_t* __restrict__ vflag, int* __restrict__ hull_area) {
+    __shared__ int sh[2 * HL_THREADS];
+    __shared__ int carry[4];                     // nearest vertex outside the block: lower / upper envelope, before / (negated) behind
+    __shared__ int row_y[HL_THREADS], row_x[HL_THREADS], row_len[HL_THREADS];     // first the flags and the mirrored scans' results
+    const int tid = threadIdx.x, total = hdr[0];
+    const int64_t q0 = (int64_t)blockIdx.x * HL_THREADS;
+    if (q0 >= total) return;                     // the whole block
+    const int q = (int)q0 + tid;
+    int r = 0, i = 0, n = 0;
+    const bool valid = q < total && pair_region(q, hdr[1], roff, rht, &r, &i, &n);
+    const int f = valid ? vflag[q] : 3;          // a pair of no region ends every scan
+    // nearest vertex at or before / at or behind the pair, inside the block (the scans towards the right run on the mirrored block)
+    const int pl = block_max_scan((f & 1) ? q : -1, sh, tid), pu = block_max_scan((f & 2) ? q : -1, sh, tid);
+    row_y[tid] = f;
+    __syncthreads();
+    const int m = HL_THREADS - 1 - tid, qm = (int)q0 + m, fm = row_y[m];       // thread tid scans for pair 255 - tid ...
+    const int sl = block_max_scan((fm & 1) ? -qm : INT_MIN, sh, tid), su = block_max_scan((fm & 2) ? -qm : INT_MIN, sh, tid);
+    row_x[m] = sl; row_len[m] = su;                                           // ... and hands the result over
+    __syncthreads();
+    const int nl = row_x[tid], nu = row_len[tid];
+    __syncthreads();
+    // ... and outside it: the block looks 256 pairs at a time until both envelopes have one
+    if (tid < 4) carry[tid] = tid < 2 ? -1 : INT_MIN;
+    __syncthreads();
+    for (int64_t c = q0 - HL_THREADS; c >= 0; c -= HL_THREADS) {
+        const int fc = vflag[c + tid];
+        if (fc & 1) atomicMax(carry + 0, (int)c + tid);
+        if (fc & 2) atomicMax(carry + 1, (int)c + tid);
+        __syncthreads();
+        const bool done = carry[0] >= 0 && carry[1] >= 0;
+        __syncthreads();
+        if (done) break;
+    }
+    for (int64_t c = q0 + HL_THREADS; c < total; c += HL_THREADS) {
+        const int fc = c + tid < total ? vflag[c + tid] : 3;
+        if (fc & 1) atomicMax(carry + 2, -((int)c + tid));
+        if (fc & 2) atomicMax(carry + 3, -((int)c + tid));
+        __syncthreads();
+        const bool done = carry[2] > INT_MIN && carry[3] > INT_MIN;
+        __syncthreads();
+        if (done) break;
+    }
+    int len = 0, xl = 0, y = 0;
+    if (valid) {
+        const int base = q - i, end = base + n - 1;           // the region's first and last pairs: vertices of both envelopes
+        const int* e = ext;
+        y = clampi(table[(int64_t)r * 6 + 2], 0, h) + i;      // < h: rht was cut to the page
+        int xr;
+        if (f & 1) xl = clampi(e[2 * (int64_t)q], 0, w - 1);
+        else {
+            const int a = clampi(pl >= 0 ? pl : carry[0], base, q - 1);
+            const int b = clampi(nl > INT_MIN ? -nl : (carry[2] > INT_MIN ? -carry[2] : end), q + 1, end);
+            xl = envelope_at(a, clampi(e[2 * (int64_t)a], 0, w - 1), b, clampi(e[2 * (int64_t)b], 0, w - 1), q, true);
+        }
+        if (f & 2) xr = clampi(e[2 * (int64_t)q + 1], 0, w - 1);
+        else {
+            const int a = clampi(pu >= 0 ? pu : carry[1], base, q - 1);
+            const int b = clampi(nu > INT_MIN ? -nu : (carry[3] > INT_MIN ? -carry[3] : end), q + 1, end);
+            xr = envelope_at(a, clampi(e[2 * (int64_t)a + 1], 0, w - 1), b, clampi(e[2 * (int64_t)b + 1], 0, w - 1), q, false);
+        }
+        xl = clampi(xl, 0, w - 1);
+        xr = clampi(xr, 0, w - 1);
+        len = xr >= xl ? xr - xl + 1 : 0;
+        if (len > 0) atomicAdd(hull_area + r, len);
+    }
+    row_y[tid] = y; row_x[tid] = xl; row_len[tid] = len;
+    __syncthreads();
+    // a wave per row: bytes up to the first 16-byte boundary, 16-byte stores, the last bytes.  Overlapping hulls store the same value.
+    const int lane = tid & 63;
+    for (int t = tid >> 6; t < HL_THREADS; t += HL_THREADS / 64) {
+        const int n1 = row_len[t];
+        if (n1 == 0) continue;
+        uint8_t* p = text + (int64_t)row_y[t] * w + row_x[t];
+        int head = (int)((16u - (unsigned)(reinterpret_cast<uintptr_t>(p) & 15u)) & 15u);
+        if (head > n1) head = n1;
+        if (lane < head) p[lane] = 1;
+        const int chunks = (n1 - head) >> 4, tail = (n1 - head) & 15;
+        uint4 ones;
+        ones.x = ones.y = ones.z = ones.w = 0x01010101u;
+        for (int c = lane; c < chunks; c += 64) *reinterpret_cast<uint4*>(p + head + 16 * c) = ones;
+        if (lane < tail) p[head + 16 * chunks + lane] = 1;
+    }
+}
+
+// ---- 6. finish -------------------------------------------------------------------------------------------------------------------
+// a block owns a 64 x 32 rectangle of one tile core (the geometry of the plane_up kernel): one atomic per block
+__global__ __launch_bounds__(HL_THREADS) void hull_finish_kernel(uint8_t* __restrict__ text, PageGrid g, int nbx, int nby, int* __restrict__ core_count) {
+    __shared__ int wave_count[HL_THREADS / 64];
+    const int tid = threadIdx.x, c = tid & 63;
+    const int t = blockIdx.x / (nbx * nby), sub = blockIdx.x % (nbx * nby);
+    const int ci = t / g.tx, cj = t % g.tx;
+    const int64_t y0 = (int64_t)ci * g.s + (sub / nbx) * HL_H, x0 = (int64_t)cj * g.s + (sub % nbx) * HL_W;
+    const int64_t yend = (int64_t)(ci + 1) * g.s < g.h ? (int64_t)(ci + 1) * g.s : g.h, xend = (int64_t)(cj + 1) * g.s < g.w ? (int64_t)(cj + 1) * g.s : g.w;
+    if (y0 >= yend || x0 >= xend) return;               // the whole block
+    int cnt = 0;
+    if (x0 + c < xend) {
+        for (int row = tid >> 6; row < HL_H && y0 + row < yend; row += HL_THREADS / 64) {
+            uint8_t* p = text + (y0 + row) * g.w + x0 + c;
+            const uint8_t v = *p;
+            if (v > 1) *p = 1;
+            cnt += v != 0;
+        }
+    }
+    if (core_count == nullptr) return;                  // the whole grid
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) cnt += __shfl_down(cnt, d);
+    if (c == 0) wave_count[tid >> 6] = cnt;
+    __syncthreads();
+    if (tid == 0) {
+        int total = 0;
+        for (int k = 0; k < HL_THREADS / 64; ++k) total += wave_count[k];
+        if (total > 0) atomicAdd(core_count + t, total);
+    }
+}
+
+}  // namespace tsii
+
+using namespace tsii;
+
+extern "C" size_t tsii_region_hulls_ws_bytes(int h, int w, int max_regions) {
+    int64_t npairs;
+    if (!hull_geometry(h, w, max_regions, &npairs)) return 0;
+    return (sizeof(int) * (size_t)(HL_HDR + 2 * (int64_t)max_regions + 2 * npairs) + (size_t)npairs + 3) / 4 * 4;
+}
+
+extern "C" int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions, int max_regions,
+                                 int tile, int halo, int* core_count, int* hull_area, void* ws, void* stream) {
+    TSII_REQUIRE(text && labels && table && n_regions && hull_area && ws, "region_hulls: null pointer");
+    int64_t npairs;
+    TSII_REQUIRE(hull_geometry(h, w, max_regions, &npairs), "region_hulls: page of %d x %d pixels, max_regions %d (h, w >= 1, h * w <= 2^31 - 2, max_regions >= 1)",
+                 h, w, max_regions);
+    TSII_REQUIRE(core_count == nullptr || grid_ok(h, w, tile, halo), "region_hulls: bad geometry h %d w %d tile %d halo %d", h, w, tile, halo);
+    TSII_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3u) == 0, "region_hulls: ws must be 4-byte aligned");
+    PageGrid g;
+    if (core_count != nullptr) g = make_grid(h, w, tile, halo);
+    else {                                              // without counts: cores of 2^20 pixels a side, no tile behind them
+        g.h = h; g.w = w; g.tile = g.s = 1 << 20; g.halo = 0;
+        g.ty = (int)cdiv64(h, g.s); g.tx = (int)cdiv64(w, g.s);
+    }
+    const int nbx = cdiv(g.s < w ? g.s : w, HL_W), nby = cdiv(g.s < h ? g.s : h, HL_H);
+    const int64_t nfinish = (int64_t)g.ty * g.tx * nbx * nby;
+    TSII_REQUIRE(nfinish < (1ll << 31), "region_hulls: bad geometry h %d w %d tile %d halo %d (too many tile cores)", h, w, tile, halo);
+    hipStream_t st = (hipStream_t)stream;
+    if (core_count != nullptr && hipMemsetAsync(core_count, 0, sizeof(int) * (size_t)g.ty * g.tx, st) != hipSuccess)
+        return check_launch("region_hulls (memset)");
+    const HullWs s = hull_ws(ws, max_regions, npairs);
+    const unsigned pair_blocks = flat_grid(npairs, HL_THREADS);
+    hipLaunchKernelGGL(hull_offsets_kernel, dim3(1), dim3(HL_THREADS), 0, st, table, n_regions, max_regions, h, npairs, s.hdr, s.roff, s.rht, hull_area);
+    hipLaunchKernelGGL(hull_init_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, s.hdr, s.ext);
+    hipLaunchKernelGGL(hull_extents_kernel, dim3(flat_grid((int64_t)h * w, HL_THREADS)), dim3(HL_THREADS), 0, st, labels, h, w, table, s.hdr, s.roff,
+                       s.rht, s.ext);
+    hipLaunchKernelGGL(hull_vertices_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, w, s.hdr, s.roff, s.rht, s.ext, s.vflag);
+    hipLaunchKernelGGL(hull_fill_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, text, h, w, table, s.hdr, s.roff, s.rht, s.ext, s.vflag, hull_area);
+    hipLaunchKernelGGL(hull_finish_kernel, dim3((unsigned)nfinish), dim3(HL_THREADS), 0, st, text, g, nbx, nby, core_count);
+    return check_launch("region_hulls");
+}

@@ -22,7 +22,7 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import _text_regions, check_region_args, unpack_regions
+from .regions import _region_hulls, _text_regions, check_region_args, unpack_hull_area, unpack_regions
 
 
 class TileGrid(NamedTuple):
@@ -213,6 +213,12 @@ class TextEraser:
     page's one synchronisation; the int32 label plane stays on the device as ``last_labels``.  With the defaults none of this runs
     and both stay ``None``.
 
+    ``hull=True`` (turns the regions path on as well) fills the convex hull of every kept region into the text plane right behind the
+    filter, as the reference demo's ``cv2.convexHull`` + ``drawContours`` does: letter counters, the gaps between glyphs and dropped
+    specks inside a text block become hole, so the filler gets one solid hole per block.  The returned mask, the tile selection, the
+    filler's holes and ``last_stats["text_pixels"]`` all see the filled plane; ``last_regions`` gains ``hull_area`` (numpy int32, the
+    pixels of each table row's hull).  Kept regions beyond ``max_regions`` get no hull.  Still one synchronisation.
+
     ``seg_long_side`` (a positive multiple of 8, like ``EvaluateSet.resize``): the segmenter sees the page resized to
     ``working_size(H, W, seg_long_side)`` -- long side ``seg_long_side``, both sides floored to a multiple of 8, Pillow's bicubic
     filter -- on that page's own tile grid; ``threshold`` and ``dilate`` act at that resolution, as in the reference, and the text
@@ -227,7 +233,7 @@ class TextEraser:
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
-                 max_regions=4096, seg_long_side=None):
+                 max_regions=4096, seg_long_side=None, hull=False):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -240,7 +246,8 @@ class TextEraser:
             raise ValueError(f"seg_long_side {seg_long_side} must be a positive multiple of 8")
         self.seg_long_side = None if seg_long_side is None else int(seg_long_side)
         self.min_area, self.connectivity, self.max_regions = int(min_area), int(connectivity), int(max_regions)
-        self.regions = bool(regions) or self.min_area > 1
+        self.hull = bool(hull)
+        self.regions = bool(regions) or self.min_area > 1 or self.hull
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -253,7 +260,7 @@ class TextEraser:
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
         self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size")
-        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only)
+        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area")
         self.last_labels = None                         # its int32 label plane, left on the device
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
@@ -283,7 +290,13 @@ class TextEraser:
 
     def _regions(self, text, g):
         """filter the text plane in place -> ONE device tensor [filtered core counts | found, kept | table]; the labels stay on the device"""
-        self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g)
+        self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g,
+                                                 tail=self.max_regions if self.hull else 0)
+        return packed
+
+    def _hulls(self, text, g, packed):
+        """fill the kept regions' hulls into the text plane in place; packed becomes [core counts of the filled plane | ... | hull_area]"""
+        _region_hulls(text, self.last_labels, packed, self.max_regions, g)
         return packed
 
     def _fill(self, page_d, text, g, selected):
@@ -323,10 +336,15 @@ class TextEraser:
                 text, counts = _text_plane_up(text, g)
             if self.regions:
                 counts = self._regions(text, g)
+                if self.hull:
+                    counts = self._hulls(text, g, counts)
             counts_h = counts.cpu().numpy()             # the one synchronisation before the download
             if self.regions:
-                counts_h, table, found, kept, truncated = unpack_regions(counts_h, g.count, self.max_regions)
+                packed_h = counts_h
+                counts_h, table, found, kept, truncated = unpack_regions(packed_h, g.count, self.max_regions)
                 self.last_regions = {"table": table, "found": found, "kept": kept, "truncated": truncated}
+                if self.hull:
+                    self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
             out, slot = self._fill(page_d, text, g, selected) if (selected and any_text) else (None, None)

@@ -4,6 +4,9 @@ The counterpart of the reference demo's ``draw_bounding_box(origin_np, mask_np, 
 text is.  One entry point, ``tsii_text_regions`` (``csrc/regions.hip``; semantics: ``include/tsii_hip.h``, "K10: text regions"); all
 integer, so the result has the same bits on every run.  ``text_regions`` is the stand-alone form; ``TextEraser`` runs the same kernels
 in place on its text plane between the mask and the tile selection (``pipeline.py``).
+
+``fill_region_hulls`` is the demo's next step, ``cv2.convexHull`` + ``cv2.drawContours(..., -1)``: the convex hull of every kept region
+filled into the plane (``tsii_region_hulls``, ``csrc/hull.hip``; "K12: region hulls"), behind the same labelling.
 """
 from typing import NamedTuple
 
@@ -12,6 +15,14 @@ import torch
 
 from . import _lib, ops
 from ._lib import call, ptr
+
+
+class RegionHulls(NamedTuple):
+    """``filled``: uint8 ``[H, W]`` of 0 / 255, the text plane with the convex hull of every kept region filled in.  ``regions``: the
+    ``TextRegions`` of the input.  ``hull_area``: numpy int32 ``[n]``, the pixels of each table row's hull."""
+    filled: object
+    regions: "TextRegions"
+    hull_area: np.ndarray
 
 
 class TextRegions(NamedTuple):
@@ -35,9 +46,10 @@ def check_region_args(connectivity, min_area, max_regions):
         raise ValueError(f"max_regions {max_regions} must be an integer >= 1")
 
 
-def _text_regions(text, connectivity, min_area, max_regions, grid=None):
+def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
     """``tsii_text_regions`` in place on the device plane ``text`` -> (labels, packed): ``packed`` is ONE int32 device tensor
-    ``[core counts (grid.count, with a grid) | found, kept | table rows]``, so that a caller reads everything back with one copy."""
+    ``[core counts (grid.count, with a grid) | found, kept | table rows | tail words]``, so that a caller reads everything back with
+    one copy (``tail``: room behind the table for ``_region_hulls``)."""
     h, w = int(text.shape[0]), int(text.shape[1])
     _lib.check_device(text.new_empty(0, dtype=torch.float32))
     assert text.dtype == torch.uint8 and text.is_contiguous()
@@ -46,12 +58,35 @@ def _text_regions(text, connectivity, min_area, max_regions, grid=None):
         raise ValueError(f"text plane of {h} x {w} pixels is out of range")
     nt = 0 if grid is None else grid.count
     labels = torch.empty((h, w), dtype=torch.int32, device=text.device)
-    packed = torch.zeros((nt + 2 + 6 * int(max_regions),), dtype=torch.int32, device=text.device)
+    packed = torch.zeros((nt + 2 + 6 * int(max_regions) + int(tail),), dtype=torch.int32, device=text.device)
     ws = ops._ws(nbytes, text)
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
     call("tsii_text_regions", ptr(text), h, w, int(connectivity), int(min_area), int(max_regions), tile, halo,
          ptr(packed[:nt]) if nt else None, ptr(labels), ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), ptr(ws), _lib.stream())
     return labels, packed
+
+
+def _region_hulls(text, labels, packed, max_regions, grid=None):
+    """``tsii_region_hulls`` in place on the device plane ``text``, right behind ``_text_regions`` (same ``grid``): ``packed`` is that
+    call's tensor grown by a ``max_regions`` tail, ``[core counts | found, kept | table | hull_area]``; the core counts at its front
+    are rewritten for the filled plane."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    nt = 0 if grid is None else grid.count
+    n = int(max_regions)
+    assert packed.numel() == nt + 2 + 7 * n and packed.dtype == torch.int32 and packed.device == text.device
+    nbytes = int(_lib.lib().tsii_region_hulls_ws_bytes(h, w, n))
+    if nbytes == 0:
+        raise ValueError(f"text plane of {h} x {w} pixels is out of range")
+    ws = ops._ws(nbytes, text)
+    tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
+    call("tsii_region_hulls", ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, tile, halo,
+         ptr(packed[:nt]) if nt else None, ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+
+
+def unpack_hull_area(packed_h, nt, max_regions, n):
+    """host copy of the grown ``packed`` -> hull_area of the ``n`` table rows in use"""
+    at = nt + 2 + 6 * int(max_regions)
+    return packed_h[at:at + n].copy()
 
 
 def unpack_regions(packed_h, nt, max_regions):
@@ -60,6 +95,36 @@ def unpack_regions(packed_h, nt, max_regions):
     n = min(kept, int(max_regions))
     table = packed_h[nt + 2:nt + 2 + 6 * n].reshape(n, 6).copy()
     return packed_h[:nt], table, found, kept, kept > n
+
+
+def _plane_on_device(text, device):
+    t = torch.from_numpy(np.ascontiguousarray(text)) if isinstance(text, np.ndarray) else text
+    if t.dim() != 2 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"text must be [H, W] uint8, got {tuple(t.shape)} {t.dtype}")
+    dev = torch.device(device) if device is not None else (t.device if t.is_cuda else torch.device("cuda:0"))
+    return t.to(dev, copy=True).contiguous()
+
+
+def _like(result, text):
+    """a device result as the same kind, on the same device, as the argument ``text``"""
+    if isinstance(text, np.ndarray):
+        return result.cpu().numpy()
+    return result if result.device == text.device else result.to(text.device)
+
+
+def fill_region_hulls(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> RegionHulls:
+    """The text plane with the convex hull of every kept region filled in: what the reference demo marks as "the text".  Arguments as
+    for ``text_regions``; regions below ``min_area`` are dropped first (a hull may cover them again), kept regions beyond
+    ``max_regions`` keep their own pixels and get no hull.  ``filled`` comes back the same kind and on the same device as ``text``,
+    which is not modified; one synchronisation (the read-back of the counts, the table and the hull areas)."""
+    check_region_args(connectivity, min_area, max_regions)
+    plane = _plane_on_device(text, device)
+    labels, packed = _text_regions(plane, connectivity, min_area, max_regions, tail=int(max_regions))
+    _region_hulls(plane, labels, packed, max_regions)
+    packed_h = packed.cpu().numpy()
+    _, table, found, kept, truncated = unpack_regions(packed_h, 0, max_regions)
+    hull_area = unpack_hull_area(packed_h, 0, max_regions, len(table))
+    return RegionHulls(_like(plane * 255, text), TextRegions(_like(labels, text), table, found, kept, truncated), hull_area)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

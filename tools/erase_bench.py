@@ -2,7 +2,7 @@
 """Times one page through TextEraser stage by stage (HIP events on the launch stream) and prints one JSON line.
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
-                                [--min-area N [--connectivity 8]] [--all-text] [--seg-long-side N]
+                                [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -16,6 +16,9 @@ timed is the cost of the pipeline, not the quality of a net.  For comparison, in
 mask and the read-back, which then carries the counts, the region counts and the table in its one copy; and ``host_route``, the same
 labelling done the usual way: download the mask, scipy.ndimage.label + find_objects + bincount (reported as unavailable without
 scipy).  ``--all-text`` makes the whole page one component: the worst case for the aggregation of areas and boxes.
+``--hull`` adds the ``hulls`` stage (tsii_region_hulls in place on the text plane, right behind the regions stage, which it turns on),
+and ``host_route_hulls``, the same step done the usual way: download the plane and the labels, ``scipy.spatial.ConvexHull`` per region,
+``PIL.ImageDraw`` polygon fill, upload again (for timing only: a drawn polygon is not the hull's exact pixel set).
 ``--seg-long-side N`` runs the segmenter at the working size ``working_size(H, W, N)`` and adds the stages ``resize``
 (tsii_page_resize_u8, between the upload and the tiles) and ``plane_up`` (tsii_text_plane_up, behind the mask); the synthetic text is
 the same blob field, sampled at the working size.  ``host_route_resample`` times the same two steps the way the reference does them:
@@ -72,6 +75,7 @@ def main(argv=None):
     ap.add_argument("--min-area", type=int, default=0, help="> 0: time the regions stage with this filter")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
     ap.add_argument("--max-regions", type=int, default=4096)
+    ap.add_argument("--hull", action="store_true", help="time the hulls stage (tsii_region_hulls) behind the regions stage")
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
     args = ap.parse_args(argv)
@@ -96,12 +100,12 @@ def main(argv=None):
     if with_seg:                                          # the same text, sampled at the working size
         field = F.interpolate(torch.from_numpy(field)[None, None], size=(hs, ws), mode="nearest")[0, 0].numpy()
     logits_fixed = tile_logits(field, gs, dev)
-    with_regions = args.min_area > 0
+    with_regions = args.min_area > 0 or args.hull
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
-                          max_regions=args.max_regions, seg_long_side=args.seg_long_side)
+                          max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -111,12 +115,14 @@ def main(argv=None):
     stages = ["upload", "page_tiles_norm", "segmenter", "tiles_text_mask", "counts_d2h", "page_tiles_fill", "filler", "compose_page_u8", "download"]
     if with_regions:
         stages.append("regions")                            # timed with its own pair of events, between the mask and the read-back
+    if args.hull:
+        stages.append("hulls")                              # its own pair of events, right behind the regions stage
     if with_seg:
         stages += ["resize", "plane_up"]                    # their own pairs of events: behind the upload / behind the mask
 
     def one_page():
         marks = [ev() for _ in range(11)]
-        reg0, reg1, res1, up0, up1 = ev(), ev(), ev(), ev(), ev()
+        reg0, reg1, hul1, res1, up0, up1 = ev(), ev(), ev(), ev(), ev(), ev()
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
@@ -140,16 +146,22 @@ def main(argv=None):
                 up1.record()
             if with_regions:
                 reg0.record()
-                _, counts = RG._text_regions(text, args.connectivity, args.min_area, args.max_regions, g)
+                counts = eraser._regions(text, g)           # tsii_text_regions; the labels stay in eraser.last_labels
                 reg1.record()
+                if args.hull:
+                    counts = eraser._hulls(text, g, counts)
+                    hul1.record()
             marks[4].record()
             counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table)
             marks[5].record()
             d2h_words = int(counts_h.size)
             region_info = None
             if with_regions:
-                counts_h, table, found, kept, truncated = RG.unpack_regions(counts_h, g.count, args.max_regions)
+                packed_h = counts_h
+                counts_h, table, found, kept, truncated = RG.unpack_regions(packed_h, g.count, args.max_regions)
                 region_info = {"found": found, "kept": kept, "truncated": truncated}
+                if args.hull:
+                    region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h, g.count, args.max_regions, len(table)).sum(dtype=np.int64))
             selected = [t for t in range(g.count) if counts_h[t] > 0]
             ids = torch.tensor(selected, dtype=torch.int32).to(dev)
             slot_h = np.full(g.count, -1, np.int32)
@@ -174,6 +186,8 @@ def main(argv=None):
         if with_regions:
             t[3] = marks[3].elapsed_time(reg0)
             t.append(reg0.elapsed_time(reg1))
+        if args.hull:
+            t.append(reg1.elapsed_time(hul1))
         if with_seg:
             t[1] = res1.elapsed_time(marks[2])
             t[3] = marks[3].elapsed_time(up0)
@@ -196,6 +210,8 @@ def main(argv=None):
         bytes_.update(resize=3 * npx + 3 * nsp, plane_up=nsp + npx)      # DESIGN.md, "working resolution"
     if with_regions:
         bytes_["regions"] = 18 * npx        # local 1 + 4, measure 4, filter 4 + 4 + 1 ("text regions"); seams and statistics on top
+    if args.hull:
+        bytes_["hulls"] = 5 * npx + n_text  # extents 4 (labels), finish 1, the fill's stores at most once per final text pixel ("region hulls")
 
     def timed(fn, sync=True):
         for _ in range(args.warmup):
@@ -273,6 +289,32 @@ def main(argv=None):
         except ImportError:
             host_route = "not available: scipy is not installed"
 
+    host_route_hulls = None
+    if args.hull:
+        text1, _ = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)
+        labels1, packed1 = RG._text_regions(text1, args.connectivity, args.min_area, args.max_regions, g)
+        table1 = RG.unpack_regions(packed1.cpu().numpy(), g.count, args.max_regions)[1]
+        try:
+            from PIL import Image, ImageDraw
+            from scipy.spatial import ConvexHull, QhullError
+
+            def host_hulls():
+                m, lab = text1.cpu().numpy(), labels1.cpu().numpy()
+                img = Image.fromarray(m * 255)
+                draw = ImageDraw.Draw(img)
+                for label, _, y0, x0, y1, x1 in table1:
+                    ys, xs = np.nonzero(lab[y0:y1, x0:x1] == label)
+                    pts = np.stack([xs + x0, ys + y0], axis=1)
+                    try:
+                        pts = pts[ConvexHull(pts).vertices]
+                    except QhullError:                      # fewer than three points, or all on one line
+                        pass
+                    draw.polygon([tuple(int(v) for v in p_) for p_ in pts], fill=255) if len(pts) > 1 else draw.point(tuple(int(v) for v in pts[0]), fill=255)
+                return torch.from_numpy(np.asarray(img) // 255).to(dev)
+            host_route_hulls = timed(host_hulls)
+        except ImportError:
+            host_route_hulls = "not available: scipy or Pillow is not installed"
+
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
         "seg_model": args.seg_model, "fill_model": args.fill_model, "tiles": g.count, "selected_tiles": n_sel,
@@ -285,7 +327,7 @@ def main(argv=None):
         "all_text": args.all_text, "min_area": args.min_area, "connectivity": args.connectivity,
         # the stages that copy to the host before the download: still one, whatever it carries
         "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
-        "regions": runs[0][5], "host_route": host_route,
+        "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
         "demo_route_mask_stage": timed(demo_mask, sync=False),
         "torch_on_device": {"page_tiles_norm": timed(torch_norm), "tiles_text_mask": timed(torch_mask), "compose_page_u8": timed(torch_compose)},
     }
