@@ -12,6 +12,8 @@ writes ``<name>_boxes.png``, the page with the boxes of the kept regions outline
 into the mask on the device (the reference demo's ``cv2.convexHull`` step), so that the inpainting net gets one solid hole per text block.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
+``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
+text block is then inpainted whole, in the middle of one window.
 """
 import argparse
 import os
@@ -57,6 +59,7 @@ def main(argv=None):
     ap.add_argument("--boxes", action="store_true", help="also write <name>_boxes.png")
     ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
+    ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
@@ -69,7 +72,7 @@ def main(argv=None):
         nets.append(net.to(dev).eval())
     eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
-                          seg_long_side=args.seg_long_side, hull=args.hull)
+                          seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -98,6 +101,9 @@ def main(argv=None):
         st = eraser.last_stats
         print("%s: %d x %d, %d of %d tiles inpainted, text fraction %.4f" %
               (name, page.shape[0], page.shape[1], st["selected"], st["tiles"], float((mask > 0).mean())))
+        if args.pack:
+            print("%s: %s, the grid would have sent %d tiles" % (name, "%d windows on the text regions" % st["windows"] if st["packed"]
+                                                                  else "no fewer windows than tiles: the grid's tiles", st["grid_selected"]))
         if "seg_size" in st:
             print("%s: segmented at %d x %d (%d tiles)" % ((name,) + tuple(st["seg_size"]) + (st["seg_tiles"],)))
     print("Runtime :{:.3f} s -> {}".format(time.time() - t0, out_folder))

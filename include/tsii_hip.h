@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 10
+#define TSII_ABI_VERSION 11
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -567,6 +567,27 @@ int tsii_page_tiles_fill(const uint8_t* page, const uint8_t* text, int h, int w,
  * The four byte planes are 4-byte aligned. */
 int tsii_compose_page_u8(const uint8_t* page, const uint8_t* text, const float* out, const int* slot, int n_sel,
                          int h, int w, int tile, int halo, uint8_t* clean, uint8_t* mask_u8, void* stream);
+
+/* Filler WINDOWS: the two entry points above with the tile grid replaced by a table.  Window k is the square of `tile` pixels a side
+ * whose first pixel is page row origin[2k], column origin[2k+1] (device int32 [n,2]; any values: negative, partly or wholly off the
+ * page, overlapping one another); tile % 32 == 0, there is no halo argument.
+ *   mask[k,r,q], img[k,r,q,c]: as tsii_page_tiles_fill, for the page pixel (origin[2k] + r, origin[2k+1] + q) -- the same element
+ * arithmetic, bit for bit: a window with a grid tile's origin equals that tile.  n >= 1, n * tile * tile / 4 < 2^31. */
+int tsii_page_windows_fill(const uint8_t* page, const uint8_t* text, int h, int w, int tile,
+                           const int* origin /* device int32 [n,2]: oy, ox */, int n,
+                           float* img /* fp32 NHWC [n,tile,tile,3] */, float* mask /* fp32 [n,tile,tile] */, void* stream);
+
+/* Compose from windows: clean uint8 [h,w,3], mask_u8 uint8 [h,w] = text * 255, as tsii_compose_page_u8.  rect: device int32 [n,4],
+ * (y0, x0, y1, x1) half-open, the page rectangle window k OWNS; rectangles may overlap.  The OWNER of a text pixel (y, x) is the
+ * lowest k with y0 <= y < y1 and x0 <= x < x1:
+ *   clean = (uint8) floorf(fmaf(min(max(out[k, y - origin[2k], x - origin[2k+1], c], 0), 1), 255, 0.5))
+ * A text pixel in no rectangle keeps its page byte, and so does one whose owner's rectangle leaves its window there (the caller keeps
+ * every rectangle inside its window; nothing is read outside out).  Bytes outside text are copied untouched.
+ * out == origin == rect == NULL with n == 0: a page without text.  n <= 1024: more is refused (-1) and nothing is launched.
+ * No workspace; the four byte planes are 4-byte aligned. */
+int tsii_compose_page_windows_u8(const uint8_t* page, const uint8_t* text, const float* out /* fp32 NHWC [n,tile,tile,3] */,
+                                 const int* origin /* [n,2] */, const int* rect /* [n,4] y0,x0,y1,x1 half-open */, int n,
+                                 int h, int w, int tile, uint8_t* clean, uint8_t* mask_u8, void* stream);
 
 /* ---- K9: validation metrics (csrc/metrics.hip).  The reference has none (it prints losses); these are this library's own. ---------
  * Besides fp32 tensors: histograms are int32, sums and SSIM values are double.  No floating-point atomics: for the same inputs and

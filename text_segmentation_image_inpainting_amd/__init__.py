@@ -12,6 +12,6 @@ from .text_segmentation import TextSegament, XceptionTextSegment  # noqa: F401,E
 from .loss import BinaryFocalLoss, FeatureExtractor, InpaintingLoss, gram_matrix, total_variation_loss  # noqa: F401,E402
 from .recipes import InpaintingRecipe, SegmentationRecipe  # noqa: F401,E402
 from .ops import activation_storage, set_activation_storage  # noqa: F401,E402
-from .pipeline import TextEraser, resize_page_u8, working_size  # noqa: F401,E402
+from .pipeline import TextEraser, plan_fill_windows, resize_page_u8, working_size  # noqa: F401,E402
 from .regions import RegionHulls, TextRegions, fill_region_hulls, text_regions  # noqa: F401,E402
 from .metrics import InpaintingMetrics, SegmentationMetrics, evaluate_inpainting, evaluate_segmentation  # noqa: F401,E402

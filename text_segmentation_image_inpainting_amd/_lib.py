@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 10          # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 11          # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -147,6 +147,8 @@ SIGNATURES = {
     "tsii_tiles_text_mask": (_i, [_p, _i, _i, _i, _i, _f, _i, _p, _p, _p]),
     "tsii_page_tiles_fill": (_i, [_p, _p, _i, _i, _i, _i, _p, _i, _p, _p, _p]),
     "tsii_compose_page_u8": (_i, [_p, _p, _p, _p, _i, _i, _i, _i, _i, _p, _p, _p]),
+    "tsii_page_windows_fill": (_i, [_p, _p, _i, _i, _i, _p, _i, _p, _p, _p]),
+    "tsii_compose_page_windows_u8": (_i, [_p, _p, _p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
     # K9 validation metrics (csrc/metrics.hip): int32 histograms, double sums; the thresholds are a HOST float array
     "tsii_seg_confusion": (_i, [_p, _p, _i, _l, _p, _i, _p, _p]),
     "tsii_inpaint_errors_ws_bytes": (_z, [_i, _i, _i, _i]),

@@ -1,7 +1,8 @@
 // K8: page-level text removal around the two networks (include/tsii_hip.h, "page pipeline"): cut a uint8 HWC page into overlapping
 // square tiles for the segmenter, turn the tiles' logits into a dilated text plane with per-tile counts, cut the filler's tiles
-// (image * mask and the mask plane) for the tiles that have text, and compose the filler's output back into the page bytes.
-// Four streaming kernels: nothing here is arithmetic bound, every choice below is about bytes and the shape of the accesses.
+// (image * mask and the mask plane) for the tiles that have text -- or for windows placed on the text regions by the host -- and
+// compose the filler's output back into the page bytes.
+// Six streaming kernels: nothing here is arithmetic bound, every choice below is about bytes and the shape of the accesses.
 //
 // Stores are plain (default cache policy), not non-temporal: every output is read next by another kernel (the nets' first layers,
 // the mask kernel, compose), and a whole page's tiles (63 MB at 1170 x 1654, tile 512 / halo 64) fit the 256 MB MALL -- a
@@ -137,29 +138,22 @@ __global__ __launch_bounds__(256) void tiles_text_mask_kernel(const float* __res
 }
 
 // ---- filler tiles ------------------------------------------------------------------------------------------------------------
-// the same thread shape as the segmenter tiles, for the listed tiles only; outside the page is a hole (mask 0, image 0)
-__global__ __launch_bounds__(256) void page_tiles_fill_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text, PageGrid g,
-                                                              const int* __restrict__ tile_ids, int nt, int total,
-                                                              float* __restrict__ img, float* __restrict__ mask) {
-    const int i = blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= total) return;
-    const int qn = g.tile >> 2;
-    const int q = i % qn, r = (i / qn) % g.tile;
-    int t = tile_ids[i / (qn * g.tile)];
-    t = t < 0 ? 0 : (t >= nt ? nt - 1 : t);           // a bad id must not become a wild read
-    const int y = (t / g.tx) * g.s - g.halo + r, x0 = (t % g.tx) * g.s - g.halo + 4 * q;
+// the same thread shape as the segmenter tiles; outside the page is a hole (mask 0, image 0).  fill_span is thread i's work once it
+// knows where its 4 pixels lie on the page: row y, columns x0 .. x0 + 3 (any of them may be off the page)
+__device__ __forceinline__ void fill_span(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text, int h, int w, int y, int x0,
+                                          int i, float* __restrict__ img, float* __restrict__ mask) {
     uint8_t b[12], tx4[4];
     bool in[4];
-    const bool row_in = y >= 0 && y < g.h;
-    if (row_in && x0 >= 0 && x0 + 3 < g.w) {
-        memcpy(b, page + ((int64_t)y * g.w + x0) * 3, 12);
-        memcpy(tx4, text + (int64_t)y * g.w + x0, 4);
+    const bool row_in = y >= 0 && y < h;
+    if (row_in && x0 >= 0 && x0 + 3 < w) {
+        memcpy(b, page + ((int64_t)y * w + x0) * 3, 12);
+        memcpy(tx4, text + (int64_t)y * w + x0, 4);
         in[0] = in[1] = in[2] = in[3] = true;
     } else {
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-            in[p] = row_in && x0 + p >= 0 && x0 + p < g.w;
-            const int64_t o = in[p] ? (int64_t)y * g.w + x0 + p : 0;
+            in[p] = row_in && x0 + p >= 0 && x0 + p < w;
+            const int64_t o = in[p] ? (int64_t)y * w + x0 + p : 0;
             tx4[p] = text[o];
             b[3 * p] = page[o * 3]; b[3 * p + 1] = page[o * 3 + 1]; b[3 * p + 2] = page[o * 3 + 2];
         }
@@ -173,6 +167,32 @@ __global__ __launch_bounds__(256) void page_tiles_fill_kernel(const uint8_t* __r
     }
     store12(img + (int64_t)i * 12, v);
     reinterpret_cast<float4*>(mask)[i] = make_float4(m[0], m[1], m[2], m[3]);
+}
+
+// the listed tiles of the grid
+__global__ __launch_bounds__(256) void page_tiles_fill_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text, PageGrid g,
+                                                              const int* __restrict__ tile_ids, int nt, int total,
+                                                              float* __restrict__ img, float* __restrict__ mask) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int qn = g.tile >> 2;
+    const int q = i % qn, r = (i / qn) % g.tile;
+    int t = tile_ids[i / (qn * g.tile)];
+    t = t < 0 ? 0 : (t >= nt ? nt - 1 : t);           // a bad id must not become a wild read
+    fill_span(page, text, g.h, g.w, (t / g.tx) * g.s - g.halo + r, (t % g.tx) * g.s - g.halo + 4 * q, i, img, mask);
+}
+
+// windows whose first pixel comes from a table: any int32 origin, on or off the page.  A coordinate far off the page is brought to
+// the nearest one that is still off it for all 4 pixels (-1 / h for the row, -4 / w for the first column), so nothing overflows.
+__global__ __launch_bounds__(256) void page_windows_fill_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text, int h, int w,
+                                                                int tile, const int* __restrict__ origin, int total,
+                                                                float* __restrict__ img, float* __restrict__ mask) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= total) return;
+    const int qn = tile >> 2;
+    const int q = i % qn, r = (i / qn) % tile, k = i / (qn * tile);
+    const int64_t y = (int64_t)origin[2 * k] + r, x0 = (int64_t)origin[2 * k + 1] + 4 * q;
+    fill_span(page, text, h, w, y < -1 ? -1 : (y > h ? h : (int)y), x0 < -4 ? -4 : (x0 > w ? w : (int)x0), i, img, mask);
 }
 
 // ---- compose -----------------------------------------------------------------------------------------------------------------
@@ -213,6 +233,59 @@ __global__ __launch_bounds__(256) void compose_page_u8_kernel(const uint8_t* __r
             uint8_t b[3] = {page[(int64_t)pix * 3], page[(int64_t)pix * 3 + 1], page[(int64_t)pix * 3 + 2]};
             const uint8_t tv = text[pix];
             if (tv && out != nullptr) compose_pixel(out, slot, n_sel, g, pix, b);
+            clean[(int64_t)pix * 3] = b[0]; clean[(int64_t)pix * 3 + 1] = b[1]; clean[(int64_t)pix * 3 + 2] = b[2];
+            mask_u8[pix] = tv ? 255 : 0;
+        }
+    }
+}
+
+// the same walk with an ownership table instead of the grid: window k owns the page rectangle rect[k] and the owner of a text pixel
+// is the LOWEST k whose rectangle holds it.  The table (6 ints a window) is staged in LDS once per block; it is searched only by
+// threads whose 4 text bytes are not all zero.
+constexpr int WIN_MAX = 1024;
+
+__device__ __forceinline__ void compose_window_pixel(const float* __restrict__ out, const int* s_rect, const int* s_org, int n, int w, int tile,
+                                                     int pix, uint8_t* rgb) {
+    const int y = pix / w, x = pix - y * w;
+    for (int k = 0; k < n; ++k) {
+        if (y < s_rect[4 * k] || x < s_rect[4 * k + 1] || y >= s_rect[4 * k + 2] || x >= s_rect[4 * k + 3]) continue;
+        const int64_t ly = (int64_t)y - s_org[2 * k], lx = (int64_t)x - s_org[2 * k + 1];
+        if (ly < 0 || ly >= tile || lx < 0 || lx >= tile) return;      // a rectangle that leaves its window must not become a wild read
+        const float* o = out + (((int64_t)k * tile + ly) * tile + lx) * 3;
+        rgb[0] = to_u8(o[0]); rgb[1] = to_u8(o[1]); rgb[2] = to_u8(o[2]);
+        return;
+    }
+}
+__global__ __launch_bounds__(256) void compose_page_windows_u8_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text,
+                                                                      const float* __restrict__ out, const int* __restrict__ origin,
+                                                                      const int* __restrict__ rect, int n, int w, int tile, int npix,
+                                                                      uint8_t* __restrict__ clean, uint8_t* __restrict__ mask_u8) {
+    __shared__ int s_rect[4 * WIN_MAX];
+    __shared__ int s_org[2 * WIN_MAX];
+    for (int k = threadIdx.x; k < 4 * n; k += blockDim.x) s_rect[k] = rect[k];
+    for (int k = threadIdx.x; k < 2 * n; k += blockDim.x) s_org[k] = origin[k];
+    __syncthreads();
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    const int p0 = 4 * i;
+    if (p0 >= npix) return;
+    if (p0 + 3 < npix) {
+        uint8_t b[12], t4[4];
+        memcpy(b, __builtin_assume_aligned(page + (int64_t)p0 * 3, 4), 12);
+        memcpy(t4, __builtin_assume_aligned(text + p0, 4), 4);
+        if (n > 0 && (t4[0] | t4[1] | t4[2] | t4[3])) {
+#pragma unroll
+            for (int p = 0; p < 4; ++p)
+                if (t4[p]) compose_window_pixel(out, s_rect, s_org, n, w, tile, p0 + p, b + 3 * p);
+        }
+#pragma unroll
+        for (int p = 0; p < 4; ++p) t4[p] = t4[p] ? 255 : 0;
+        memcpy(__builtin_assume_aligned(clean + (int64_t)p0 * 3, 4), b, 12);
+        memcpy(__builtin_assume_aligned(mask_u8 + p0, 4), t4, 4);
+    } else {
+        for (int pix = p0; pix < npix; ++pix) {
+            uint8_t b[3] = {page[(int64_t)pix * 3], page[(int64_t)pix * 3 + 1], page[(int64_t)pix * 3 + 2]};
+            const uint8_t tv = text[pix];
+            if (tv && n > 0) compose_window_pixel(out, s_rect, s_org, n, w, tile, pix, b);
             clean[(int64_t)pix * 3] = b[0]; clean[(int64_t)pix * 3 + 1] = b[1]; clean[(int64_t)pix * 3 + 2] = b[2];
             mask_u8[pix] = tv ? 255 : 0;
         }
@@ -282,4 +355,35 @@ extern "C" int tsii_compose_page_u8(const uint8_t* page, const uint8_t* text, co
     hipLaunchKernelGGL(compose_page_u8_kernel, dim3(flat_grid(cdiv(npix, 4), 256)), dim3(256), 0, (hipStream_t)stream,
                        page, text, out, slot, n_sel, g, npix, clean, mask_u8);
     return check_launch("compose_page_u8");
+}
+
+// the page, the tile side and the windows' volume as the grid entry points bound them; halo plays no part
+static inline bool windows_ok(int h, int w, int tile) {
+    return h > 0 && w > 0 && tile > 0 && tile % 32 == 0 && (int64_t)h * w < (1ll << 31) - 4;
+}
+
+extern "C" int tsii_page_windows_fill(const uint8_t* page, const uint8_t* text, int h, int w, int tile, const int* origin, int n,
+                                      float* img, float* mask, void* stream) {
+    TSII_REQUIRE(page && text && origin && img && mask, "page_windows_fill: null pointer");
+    TSII_REQUIRE(windows_ok(h, w, tile), "page_windows_fill: bad geometry h %d w %d tile %d (tile %% 32 == 0)", h, w, tile);
+    TSII_REQUIRE(n > 0 && (int64_t)n * tile * (tile / 4) < (1ll << 31), "page_windows_fill: %d windows of %d", n, tile);
+    TSII_REQUIRE(aligned16(img) && aligned16(mask), "page_windows_fill: outputs must be 16-byte aligned");
+    const int total = n * tile * (tile / 4);
+    hipLaunchKernelGGL(page_windows_fill_kernel, dim3(flat_grid(total, 256)), dim3(256), 0, (hipStream_t)stream,
+                       page, text, h, w, tile, origin, total, img, mask);
+    return check_launch("page_windows_fill");
+}
+
+extern "C" int tsii_compose_page_windows_u8(const uint8_t* page, const uint8_t* text, const float* out, const int* origin, const int* rect,
+                                            int n, int h, int w, int tile, uint8_t* clean, uint8_t* mask_u8, void* stream) {
+    TSII_REQUIRE(page && text && clean && mask_u8, "compose_page_windows_u8: null pointer");
+    TSII_REQUIRE(n >= 0 && n <= WIN_MAX, "compose_page_windows_u8: %d windows (at most %d)", n, WIN_MAX);
+    TSII_REQUIRE((out == nullptr) == (n == 0) && (origin == nullptr) == (n == 0) && (rect == nullptr) == (n == 0),
+                 "compose_page_windows_u8: out, origin, rect and n > 0 come together");
+    TSII_REQUIRE(windows_ok(h, w, tile), "compose_page_windows_u8: bad geometry h %d w %d tile %d (tile %% 32 == 0)", h, w, tile);
+    TSII_REQUIRE(aligned4(page) && aligned4(text) && aligned4(clean) && aligned4(mask_u8), "compose_page_windows_u8: byte planes must be 4-byte aligned");
+    const int npix = h * w;
+    hipLaunchKernelGGL(compose_page_windows_u8_kernel, dim3(flat_grid(cdiv(npix, 4), 256)), dim3(256), 0, (hipStream_t)stream,
+                       page, text, out, origin, rect, n, w, tile, npix, clean, mask_u8);
+    return check_launch("compose_page_windows_u8");
 }

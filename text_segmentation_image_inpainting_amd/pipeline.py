@@ -3,13 +3,16 @@
 ``TextEraser`` cuts a uint8 page of any size into overlapping square tiles, runs a segmentation net on them, turns the logits
 into a dilated text plane, sends only the tiles that contain text through an inpainting net, and writes the inpainted pixels back
 into the page bytes.  The page is uploaded once as uint8 and downloaded once as uint8; everything between stays on the device, in
-the four kernels of ``csrc/pipeline.hip`` (semantics: ``include/tsii_hip.h``, "K8: page pipeline") and the two nets.  Inference
+the kernels of ``csrc/pipeline.hip`` (semantics: ``include/tsii_hip.h``, "K8: page pipeline") and the two nets.  Inference
 only: nothing here records autograd.
 
 With ``seg_long_side`` the segmenter works at its own resolution, as the reference's ``EvaluateSet`` has it: the page is resized on
 the device with Pillow's bicubic filter, byte for byte, and the working-resolution text plane comes back onto the page's grid with
 "bilinear, then ``> 0``" in integers (``csrc/resample.hip``; "K11: working resolution").  The inpainting net always sees the page's
 own pixels.
+
+With ``pack`` the filler's tiles are no longer those of the grid that have text but windows centred on the text regions, placed on the
+host by ``plan_fill_windows`` from the region boxes that the page's one synchronisation brings back anyway.
 """
 from contextlib import contextmanager
 from typing import NamedTuple
@@ -101,6 +104,68 @@ def _compose_page_u8(page, text, out, slot, g: TileGrid, clean, mask_u8):
     _same_device(page, text, clean, mask_u8, *([] if out is None else [out, slot]))
     call("tsii_compose_page_u8", ptr(page), ptr(text), ptr(out), ptr(slot), ns, g.h, g.w, g.tile, g.halo, ptr(clean), ptr(mask_u8),
          _lib.stream())
+
+
+def _page_windows_fill(page, text, g: TileGrid, origin):
+    n = int(origin.shape[0])
+    img = torch.empty((n, g.tile, g.tile, 3), dtype=torch.float32, device=page.device)
+    mask = torch.empty((n, g.tile, g.tile), dtype=torch.float32, device=page.device)
+    _same_device(img, mask, page, text, origin)
+    call("tsii_page_windows_fill", ptr(page), ptr(text), g.h, g.w, g.tile, ptr(origin), n, ptr(img), ptr(mask), _lib.stream())
+    return img, mask
+
+
+def _compose_page_windows_u8(page, text, out, origin, rect, g: TileGrid, clean, mask_u8):
+    n = int(out.shape[0])
+    assert out.shape == (n, g.tile, g.tile, 3) and origin.shape == (n, 2) and rect.shape == (n, 4)
+    _same_device(page, text, clean, mask_u8, out, origin, rect)
+    call("tsii_compose_page_windows_u8", ptr(page), ptr(text), ptr(out), ptr(origin), ptr(rect), n, g.h, g.w, g.tile, ptr(clean),
+         ptr(mask_u8), _lib.stream())
+
+
+MAX_FILL_WINDOWS = 1024         # what tsii_compose_page_windows_u8 accepts
+
+
+def plan_fill_windows(boxes, h, w, tile, halo):
+    """Filler windows for the text regions of an ``h x w`` page: ``(origins, rects)``, int32 ``[m, 2]`` (page row and column of each
+    window's first pixel) and int32 ``[m, 4]`` (``y0, x0, y1, x1``, half-open: the page rectangle each window owns).  ``boxes``: int
+    ``[n, 4]`` of ``(y0, x0, y1, x1)``, half-open, inside the page -- the box columns of a region table.  Pure host code.
+
+    With ``S = tile - 2 * halo``: the rects cover every box; each is non-empty, inside the page, at most ``S`` a side and inside its
+    window, at least ``halo`` pixels from every window edge that is not at or beyond the page edge.  Where the page side is at least
+    ``tile`` the origin lies in ``[0, side - tile]`` (no window pixel is spent beyond the page), else it is ``-((tile - side) // 2)``.
+    Rects of different windows may overlap; the lowest index owns a pixel.  The same boxes give the same windows.
+
+    Greedy: boxes larger than ``S`` are cut into ``S x S`` pieces from their own corner; the pieces, sorted by ``(y0, x0)``, each join
+    the first window whose bounding box stays within ``S x S`` with them, or open a new one; a window is centred on its box."""
+    g = tile_grid(h, w, tile, halo)
+    s = g.stride
+    boxes = np.asarray(boxes, dtype=np.int64).reshape(-1, 4)
+    pieces = []
+    for y0, x0, y1, x1 in boxes.tolist():
+        if not (0 <= y0 < y1 <= g.h and 0 <= x0 < x1 <= g.w):
+            raise ValueError(f"box ({y0}, {x0}, {y1}, {x1}) is empty or leaves the {g.h} x {g.w} page")
+        pieces += [(py, px, min(py + s, y1), min(px + s, x1)) for py in range(y0, y1, s) for px in range(x0, x1, s)]
+    pieces.sort()
+    wins, first_open = [], 0        # windows before first_open start S rows or more above the current piece: nothing can join them any more
+    for y0, x0, y1, x1 in pieces:
+        while first_open < len(wins) and wins[first_open][0] + s <= y0:
+            first_open += 1
+        for win in wins[first_open:]:
+            u = (win[0], min(win[1], x0), max(win[2], y1), max(win[3], x1))      # win[0] <= y0: the pieces come sorted
+            if u[2] - u[0] <= s and u[3] - u[1] <= s:
+                win[:] = u
+                break
+        else:
+            wins.append([y0, x0, y1, x1])
+    rects = np.asarray(wins, dtype=np.int32).reshape(-1, 4)
+
+    def origin(start, extent, side):
+        if side < tile:
+            return np.full_like(start, -((tile - side) // 2))
+        return np.clip(start - (tile - extent) // 2, 0, side - tile)
+    origins = np.stack([origin(rects[:, 0], rects[:, 2] - rects[:, 0], g.h), origin(rects[:, 1], rects[:, 3] - rects[:, 1], g.w)], axis=1)
+    return origins.astype(np.int32), rects
 
 
 def working_size(h, w, long_side):
@@ -233,7 +298,7 @@ class TextEraser:
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
-                 max_regions=4096, seg_long_side=None, hull=False):
+                 max_regions=4096, seg_long_side=None, hull=False, pack=False):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -246,8 +311,10 @@ class TextEraser:
             raise ValueError(f"seg_long_side {seg_long_side} must be a positive multiple of 8")
         self.seg_long_side = None if seg_long_side is None else int(seg_long_side)
         self.min_area, self.connectivity, self.max_regions = int(min_area), int(connectivity), int(max_regions)
-        self.hull = bool(hull)
-        self.regions = bool(regions) or self.min_area > 1 or self.hull
+        self.hull, self.pack = bool(hull), bool(pack)
+        if self.pack and not skip_blank_tiles:
+            raise ValueError("pack=True places the filler's windows on the text: it needs skip_blank_tiles=True")
+        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -259,7 +326,7 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size")
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected")
         self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area")
         self.last_labels = None                         # its int32 label plane, left on the device
 
@@ -299,14 +366,10 @@ class TextEraser:
         _region_hulls(text, self.last_labels, packed, self.max_regions, g)
         return packed
 
-    def _fill(self, page_d, text, g, selected):
-        ids = torch.tensor(selected, dtype=torch.int32).to(self.device)
-        slot_h = np.full(g.count, -1, np.int32)
-        slot_h[selected] = np.arange(len(selected), dtype=np.int32)
-        slot = torch.from_numpy(slot_h).to(self.device)
-        img, mplane = _page_tiles_fill(page_d, text, g, ids)
+    def _run_filler(self, img, mplane, g):
+        """fp32 NHWC tiles and their mask planes through the filler, ``tile_batch`` at a time -> its outputs, fp32 NHWC"""
         x = img.permute(0, 3, 1, 2)
-        ns, out = len(selected), None
+        ns, out = int(img.shape[0]), None
         for b0 in range(0, ns, self.tile_batch):
             n = min(self.tile_batch, ns - b0)
             ob = self.filler((x[b0:b0 + n], MaskParts.from_plane(mplane[b0:b0 + n], 3)))
@@ -318,7 +381,27 @@ class TextEraser:
                 if out is None:
                     out = torch.empty((ns, g.tile, g.tile, 3), dtype=torch.float32, device=self.device)
                 out[b0:b0 + n].copy_(ob.permute(0, 2, 3, 1))
-        return out, slot
+        return out
+
+    def _fill(self, page_d, text, g, selected):
+        ids = torch.tensor(selected, dtype=torch.int32).to(self.device)
+        slot_h = np.full(g.count, -1, np.int32)
+        slot_h[selected] = np.arange(len(selected), dtype=np.int32)
+        slot = torch.from_numpy(slot_h).to(self.device)
+        img, mplane = _page_tiles_fill(page_d, text, g, ids)
+        return self._run_filler(img, mplane, g), slot
+
+    def _plan(self, table, truncated, g, n_grid):
+        """the windows to use instead of the grid's ``n_grid`` tiles -> (origins, rects) on the host, or None: stay on the grid"""
+        if truncated or n_grid < 2:                     # regions beyond the table have no box; one tile cannot become fewer
+            return None
+        origins, rects = plan_fill_windows(table[:, 2:6], g.h, g.w, g.tile, g.halo)
+        return (origins, rects) if 0 < len(origins) <= MAX_FILL_WINDOWS and len(origins) < n_grid else None
+
+    def _fill_windows(self, page_d, text, g, origins, rects):
+        origin, rect = torch.from_numpy(origins).to(self.device), torch.from_numpy(rects).to(self.device)
+        img, mplane = _page_windows_fill(page_d, text, g, origin)
+        return self._run_filler(img, mplane, g), origin, rect
 
     def _erase(self, page):
         page_d = self._upload(page)
@@ -347,12 +430,22 @@ class TextEraser:
                     self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
-            out, slot = self._fill(page_d, text, g, selected) if (selected and any_text) else (None, None)
+            windows = self._plan(table, truncated, g, len(selected)) if (self.pack and any_text) else None
+            if windows is not None:
+                out, origin, rect = self._fill_windows(page_d, text, g, *windows)
+            else:
+                out, slot = self._fill(page_d, text, g, selected) if (selected and any_text) else (None, None)
             off = (h * w * 3 + 15) // 16 * 16           # clean + mask in one buffer (one download); the kernel wants both 4-byte aligned
             both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
             clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
-            _compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
-        self.last_stats = {"tiles": g.count, "selected": len(selected) if out is not None else 0, "text_pixels": int(counts_h.sum())}
+            if windows is not None:
+                _compose_page_windows_u8(page_d, text, out, origin, rect, g, clean, mask_u8)
+            else:
+                _compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
+        self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0, "text_pixels": int(counts_h.sum())}
+        if self.pack:
+            self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
+                                   grid_selected=len(selected) if any_text else 0)
         if self.seg_long_side is not None:
             self.last_stats.update(seg_tiles=gs.count, seg_size=(gs.h, gs.w))
         if isinstance(page, np.ndarray):

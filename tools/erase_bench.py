@@ -2,7 +2,7 @@
 """Times one page through TextEraser stage by stage (HIP events on the launch stream) and prints one JSON line.
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
-                                [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N]
+                                [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -23,6 +23,11 @@ and ``host_route_hulls``, the same step done the usual way: download the plane a
 (tsii_page_resize_u8, between the upload and the tiles) and ``plane_up`` (tsii_text_plane_up, behind the mask); the synthetic text is
 the same blob field, sampled at the working size.  ``host_route_resample`` times the same two steps the way the reference does them:
 download the page, ``PIL.Image.resize(BICUBIC)``, upload; download the working mask, ``interpolate(bilinear) > 0``, upload.
+``--pack`` (turns the regions stage on) places the filler's windows on the text regions: the host's ``plan_fill_windows`` is timed with
+the host clock (``plan_host_ms``, behind the read-back, so nothing else is in flight), and where the windows are fewer than the grid's
+tiles the stages ``page_tiles_fill`` / ``compose_page_u8`` are replaced by ``page_windows_fill`` / ``compose_page_windows_u8``
+(tsii_page_windows_fill, tsii_compose_page_windows_u8); ``filler_tiles`` reports both counts.  Compare with a run without ``--pack`` in
+the same session (same ``--min-area``).
 """
 import argparse
 import json
@@ -78,6 +83,7 @@ def main(argv=None):
     ap.add_argument("--hull", action="store_true", help="time the hulls stage (tsii_region_hulls) behind the regions stage")
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
+    ap.add_argument("--pack", action="store_true", help="windows on the text regions instead of the grid's tiles (turns the regions stage on)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
@@ -100,12 +106,12 @@ def main(argv=None):
     if with_seg:                                          # the same text, sampled at the working size
         field = F.interpolate(torch.from_numpy(field)[None, None], size=(hs, ws), mode="nearest")[0, 0].numpy()
     logits_fixed = tile_logits(field, gs, dev)
-    with_regions = args.min_area > 0 or args.hull
+    with_regions = args.min_area > 0 or args.hull or args.pack
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
-                          max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull)
+                          max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -163,20 +169,33 @@ def main(argv=None):
                 if args.hull:
                     region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h, g.count, args.max_regions, len(table)).sum(dtype=np.int64))
             selected = [t for t in range(g.count) if counts_h[t] > 0]
-            ids = torch.tensor(selected, dtype=torch.int32).to(dev)
-            slot_h = np.full(g.count, -1, np.int32)
-            slot_h[selected] = np.arange(len(selected), dtype=np.int32)
-            slot = torch.from_numpy(slot_h).to(dev)
+            windows, plan_ms = None, 0.0
+            if args.pack:
+                t0 = time.perf_counter()
+                windows = eraser._plan(table, truncated, g, len(selected))
+                plan_ms = (time.perf_counter() - t0) * 1e3
+            if windows is not None:
+                origin, rect = torch.from_numpy(windows[0]).to(dev), torch.from_numpy(windows[1]).to(dev)
+                n_fill = len(windows[0])
+            else:
+                ids = torch.tensor(selected, dtype=torch.int32).to(dev)
+                slot_h = np.full(g.count, -1, np.int32)
+                slot_h[selected] = np.arange(len(selected), dtype=np.int32)
+                slot = torch.from_numpy(slot_h).to(dev)
+                n_fill = len(selected)
             marks[10].record()                              # the two small uploads above belong to no stage
-            img, mplane = P._page_tiles_fill(page_d, text, g, ids)
+            img, mplane = P._page_windows_fill(page_d, text, g, origin) if windows is not None else P._page_tiles_fill(page_d, text, g, ids)
             marks[6].record()
             xi = img.permute(0, 3, 1, 2)
             outs = [P.to_nhwc(fil((xi[b:b + args.tile_batch], P.MaskParts.from_plane(mplane[b:b + args.tile_batch], 3))))
-                    for b in range(0, len(selected), args.tile_batch)]
+                    for b in range(0, n_fill, args.tile_batch)]
             out = outs[0] if len(outs) == 1 else torch.cat(outs)
             marks[7].record()
             clean, mask_u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev), torch.empty((h, w), dtype=torch.uint8, device=dev)
-            P._compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
+            if windows is not None:
+                P._compose_page_windows_u8(page_d, text, out, origin, rect, g, clean, mask_u8)
+            else:
+                P._compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
             marks[8].record()
             clean.cpu(), mask_u8.cpu()
             marks[9].record()
@@ -192,12 +211,15 @@ def main(argv=None):
             t[1] = res1.elapsed_time(marks[2])
             t[3] = marks[3].elapsed_time(up0)
             t += [marks[1].elapsed_time(res1), up0.elapsed_time(up1)]
-        return t, len(selected), int(counts_h.sum()), (page_d, text, out, slot, tiles, text_s), d2h_words, region_info
+        return t, len(selected), int(counts_h.sum()), (page_d, text, out, tiles, text_s), d2h_words, region_info, windows, plan_ms
 
     for _ in range(args.warmup):
         one_page()
     runs = [one_page() for _ in range(args.repeats)]
-    n_sel, n_text, keep = runs[0][1], runs[0][2], runs[0][3]
+    n_sel, n_text, keep, windows = runs[0][1], runs[0][2], runs[0][3], runs[0][6]
+    n_fill = n_sel if windows is None else len(windows[0])
+    if windows is not None:                                 # the same two slots of the timeline, other kernels
+        stages[stages.index("page_tiles_fill")], stages[stages.index("compose_page_u8")] = "page_windows_fill", "compose_page_windows_u8"
     ms = {s: [r[0][i] for r in runs] for i, s in enumerate(stages)}
     med = {s: statistics.median(v) for s, v in ms.items()}
 
@@ -206,6 +228,11 @@ def main(argv=None):
     nsp = hs * ws
     bytes_ = {"page_tiles_norm": 3 * nsp + 12 * gs.count * tpx, "tiles_text_mask": 5 * nsp,
               "page_tiles_fill": 4 * npx * n_sel / g.count + 16 * n_sel * tpx, "compose_page_u8": 8 * npx + 12 * n_text}
+    if windows is not None:                                 # DESIGN.md, "packed filler windows": 4 bytes read per window pixel on the page
+        oy, ox = windows[0][:, 0].astype(np.int64), windows[0][:, 1].astype(np.int64)
+        on_page = int(((np.minimum(oy + args.tile, h) - np.maximum(oy, 0)) * (np.minimum(ox + args.tile, w) - np.maximum(ox, 0))).sum())
+        del bytes_["page_tiles_fill"], bytes_["compose_page_u8"]
+        bytes_.update(page_windows_fill=4 * on_page + 16 * n_fill * tpx, compose_page_windows_u8=8 * npx + 12 * n_text)
     if with_seg:
         bytes_.update(resize=3 * npx + 3 * nsp, plane_up=nsp + npx)      # DESIGN.md, "working resolution"
     if with_regions:
@@ -226,7 +253,7 @@ def main(argv=None):
             vals.append((time.perf_counter() - t0) * 1e3)
         return {"median_ms": round(statistics.median(vals), 4), "min_ms": round(min(vals), 4), "max_ms": round(max(vals), 4)}
 
-    page_d, text, out, slot, tiles, text_s = keep
+    page_d, text, out, tiles, text_s = keep
     # (a) the parent's route for the mask stage: the page's logits to the host, threshold + 3 x 3 max-pool with nine torch.maximum
     stitched = torch.randn(1, 1, h, w, device=dev)
 
@@ -328,6 +355,9 @@ def main(argv=None):
         # the stages that copy to the host before the download: still one, whatever it carries
         "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
         "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
+        "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
+        "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
+                                                    "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
         "demo_route_mask_stage": timed(demo_mask, sync=False),
         "torch_on_device": {"page_tiles_norm": timed(torch_norm), "tiles_text_mask": timed(torch_mask), "compose_page_u8": timed(torch_compose)},
     }
