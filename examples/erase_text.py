@@ -14,6 +14,8 @@ into the mask on the device (the reference demo's ``cv2.convexHull`` step), so t
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 ``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
 text block is then inpainted whole, in the middle of one window.
+``--flat T`` (0..255) paints the text regions whose surroundings (``--flat-ring N`` pixels around them, default 3) are of one colour within
+T grey levels -- lettering in a speech bubble -- with that colour on the device; only the text over artwork goes to the inpainting net.
 """
 import argparse
 import os
@@ -60,6 +62,8 @@ def main(argv=None):
     ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
+    ap.add_argument("--flat", type=int, default=None, metavar="T", help="paint text regions whose surroundings are uniform within T grey levels")
+    ap.add_argument("--flat-ring", type=int, default=3, metavar="N", help="width of the ring of surrounding pixels --flat looks at (1..8)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
@@ -72,7 +76,7 @@ def main(argv=None):
         nets.append(net.to(dev).eval())
     eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
-                          seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack)
+                          seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -104,6 +108,8 @@ def main(argv=None):
         if args.pack:
             print("%s: %s, the grid would have sent %d tiles" % (name, "%d windows on the text regions" % st["windows"] if st["packed"]
                                                                   else "no fewer windows than tiles: the grid's tiles", st["grid_selected"]))
+        if args.flat is not None:
+            print("%s: %d flat text regions (%d pixels) painted without the inpainting net" % (name, st["flat_regions"], st["flat_pixels"]))
         if "seg_size" in st:
             print("%s: segmented at %d x %d (%d tiles)" % ((name,) + tuple(st["seg_size"]) + (st["seg_tiles"],)))
     print("Runtime :{:.3f} s -> {}".format(time.time() - t0, out_folder))

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 11
+#define TSII_ABI_VERSION 12
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -725,6 +725,44 @@ int tsii_text_plane_up(const uint8_t* text_s, int hs, int ws, int h, int w, int 
 size_t tsii_region_hulls_ws_bytes(int h, int w, int max_regions);
 int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions, int max_regions,
                       int tile, int halo, int* core_count, int* hull_area, void* ws, void* stream);
+
+/* ---- K13: flat regions (csrc/flat.hip) -- the reference README's middle step, "use the generated mask to white out words", for the text
+ * that sits on one flat colour (a speech bubble): a region whose surrounding RING of page pixels is uniform within `tol` grey levels is
+ * painted with the ring's mean colour on the device and leaves the text plane; only what is left goes to an inpainting net.  All integer
+ * (the channel sums in 64 bits): exact for every page tsii_text_regions accepts, the same bits on every run.
+ * Inputs: page uint8 [h,w,3]; text uint8 [h,w] (non-zero = text), REWRITTEN IN PLACE; labels int32 [h,w], table int32 [max_regions,6] and
+ * n_regions int32 [2] ON THE DEVICE exactly as tsii_text_regions leaves them FOR THIS VERY PLANE (every text pixel has a non-zero label;
+ * a plane changed since, by tsii_region_hulls for one, is labelled again first); ring 1..8; tol 0..255.  Only the label column of the
+ * table is read.  R = min(n_regions[1], max_regions); for r < R:
+ *   C_r      the pixels whose label is table[r][0]
+ *   Ring_r   the page pixels q with text[q] == 0 on entry for which some p in C_r has max(|qy - py|, |qx - px|) <= ring.  A pixel may lie
+ *            in several rings; pixels of other regions (in the table or not) lie in none; the page edge clips the ring
+ *   n_r = |Ring_r|;  lo_c, hi_c, sum_c per channel c: minimum, maximum and sum of the ORIGINAL page bytes over Ring_r
+ *   flat_r   iff n_r >= 1 and hi_c - lo_c <= tol for all three channels
+ *   colour_r[c] = (2 sum_c + n_r) / (2 n_r) in integer division (the mean, halves rounded up); 0 where n_r == 0
+ * Outputs:
+ *   painted, uint8 [h,w,3] (not the page itself): colour_r on C_r where flat_r holds, the page byte everywhere else
+ *   text[p]  = 0 on the flat regions, 1 where it was non-zero otherwise, else 0.  Regions beyond the table (kept > max_regions) are never
+ *              flat and stay text
+ *   mask, uint8 [h,w] or NULL: 255 where text was non-zero ON ENTRY, else 0 -- the mask of everything that is removed, painted or
+ *              inpainted.  (tsii_compose_page_u8 and tsii_compose_page_windows_u8 keep their behaviour: behind this call they get
+ *              `painted` as their page and the reduced plane, their own mask output -- of the reduced plane -- goes to a scratch buffer
+ *              and this one is the page's mask.)
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the text pixels of
+ *              the FINAL plane in each tile core (integer atomics: independent of block order)
+ *   flat, int32 [max_regions,5]: row r < R = {flat_r, colour_r[0], colour_r[1], colour_r[2], n_r}; the rows behind R are not touched
+ *   labels, table and n_regions are read only.
+ * No allocation, no host synchronisation, everything on the caller's stream; no grid-wide barrier and no waiting on another block.
+ * ws: tsii_flat_regions_ws_bytes(h, w, max_regions) bytes (0: geometry refused), 8-BYTE aligned; it depends on (h, w, max_regions) only,
+ * needs nothing cleared beforehand and holds nothing a later call depends on.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1; h*w > 2^31 - 2; max_regions < 1; ring outside 1..8; tol outside
+ * 0..255; a NULL among page, text, labels, table, n_regions, painted, flat, ws; painted == page; a bad tile geometry while
+ * core_count != NULL.  The count read from n_regions is clamped to max_regions and every table row is found by a search below it: a
+ * table that does not belong to the labels gives wrong bytes, never an access outside the buffers. */
+size_t tsii_flat_regions_ws_bytes(int h, int w, int max_regions);
+int tsii_flat_regions(const uint8_t* page, uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
+                      int max_regions, int ring, int tol, int tile, int halo, int* core_count, uint8_t* painted, uint8_t* mask,
+                      int* flat, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

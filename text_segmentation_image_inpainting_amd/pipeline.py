@@ -13,6 +13,10 @@ own pixels.
 
 With ``pack`` the filler's tiles are no longer those of the grid that have text but windows centred on the text regions, placed on the
 host by ``plan_fill_windows`` from the region boxes that the page's one synchronisation brings back anyway.
+
+With ``flat`` the text regions that sit on one flat colour -- lettering in a speech bubble -- are painted with that colour on the device
+(``csrc/flat.hip``; "K13: flat regions") and never reach the filler: the reference README's "use the generated mask to white out
+words", applied where nothing has to be inferred.
 """
 from contextlib import contextmanager
 from typing import NamedTuple
@@ -25,7 +29,8 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import _region_hulls, _text_regions, check_region_args, unpack_hull_area, unpack_regions
+from .regions import (_flat_regions, _region_hulls, _text_regions, check_flat_args, check_region_args, unpack_flat, unpack_hull_area,
+                      unpack_regions)
 
 
 class TileGrid(NamedTuple):
@@ -291,6 +296,17 @@ class TextEraser:
     the filler work in page pixels.  A side of the page may be at most 8 x its working side (and the other way round).
     ``last_stats`` then also has ``seg_tiles`` and ``seg_size``.  ``None`` (the default): the page's own resolution, none of this runs.
 
+    ``flat=T`` (an integer 0..255; turns the regions path on as well): a text region whose ring of surrounding page pixels -- those
+    within ``flat_ring`` (1..8) pixels of it that are not text themselves -- is uniform within ``T`` grey levels in every channel is
+    painted with the ring's mean colour on the device, right behind the filter (and the hulls; the filled plane is labelled once more
+    for it, since hull pixels carry no label).  Such a region selects no tile, is no hole for the filler -- which sees the painted
+    pixels as valid context -- and is not among the boxes ``pack`` places its windows on; a page whose text is all flat never calls the
+    filler.  The returned mask still holds every region, flat or not.  ``last_stats`` gains ``flat_regions`` and ``flat_pixels``
+    (``text_pixels`` stays the count of the returned mask), ``last_regions`` gains ``flat``: a dict of ``table`` (the labelled
+    components the stage worked on: ``last_regions["table"]`` itself without ``hull``), ``is_flat``, ``colour`` (uint8 ``[n, 3]``) and
+    ``ring_pixels``.  Regions without a ring and kept regions beyond ``max_regions`` are never flat.  Still one synchronisation.
+    ``None`` (the default): none of this runs.
+
     The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
     the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
     ``clean`` equals the page wherever ``mask`` is 0.
@@ -298,7 +314,7 @@ class TextEraser:
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
-                 max_regions=4096, seg_long_side=None, hull=False, pack=False):
+                 max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -314,7 +330,10 @@ class TextEraser:
         self.hull, self.pack = bool(hull), bool(pack)
         if self.pack and not skip_blank_tiles:
             raise ValueError("pack=True places the filler's windows on the text: it needs skip_blank_tiles=True")
-        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack
+        if flat is not None or flat_ring != 3:
+            check_flat_args(0 if flat is None else flat, flat_ring)
+        self.flat, self.flat_ring = None if flat is None else int(flat), int(flat_ring)
+        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack or self.flat is not None
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -326,8 +345,8 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected")
-        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area")
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels")
+        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat")
         self.last_labels = None                         # its int32 label plane, left on the device
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
@@ -358,13 +377,27 @@ class TextEraser:
     def _regions(self, text, g):
         """filter the text plane in place -> ONE device tensor [filtered core counts | found, kept | table]; the labels stay on the device"""
         self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g,
-                                                 tail=self.max_regions if self.hull else 0)
+                                                 tail=self.max_regions if self.hull else (5 * self.max_regions if self.flat is not None else 0))
         return packed
 
     def _hulls(self, text, g, packed):
         """fill the kept regions' hulls into the text plane in place; packed becomes [core counts of the filled plane | ... | hull_area]"""
         _region_hulls(text, self.last_labels, packed, self.max_regions, g)
         return packed
+
+    def _flat(self, page_d, text, g, packed, mask_u8):
+        """paint the flat regions and take them out of the text plane in place -> (ONE device tensor for the read-back, the number of
+        its leading words that belong to the stages before, the painted page); ``mask_u8`` gets the mask of the whole plane.  Behind the
+        hulls the filled plane is labelled once more and that call's tensor ``[core counts | found, kept | table | flat rows]`` rides
+        behind ``packed``; otherwise the flat rows are the tail of ``packed`` itself.  The core counts of the reduced plane are at the
+        front of the part behind ``split``."""
+        labels, own, split = self.last_labels, packed, 0
+        if self.hull:
+            labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=5 * self.max_regions)
+            split = int(packed.numel())
+        painted = torch.empty_like(page_d)
+        _flat_regions(page_d, text, labels, own, self.max_regions, self.flat_ring, self.flat, painted, mask_u8, g)
+        return (torch.cat([packed, own]) if split else packed), split, painted
 
     def _run_filler(self, img, mplane, g):
         """fp32 NHWC tiles and their mask planes through the filler, ``tile_batch`` at a time -> its outputs, fp32 NHWC"""
@@ -417,32 +450,47 @@ class TextEraser:
             text, counts = _tiles_text_mask(logits, gs, self.logit_threshold, self.dilate)
             if gs is not g:
                 text, counts = _text_plane_up(text, g)
+            off = (h * w * 3 + 15) // 16 * 16           # clean + mask in one buffer (one download); the kernels want both 4-byte aligned
+            both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
+            clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
+            src, compose_mask, split = page_d, mask_u8, 0   # src: the page the filler and compose see
             if self.regions:
                 counts = self._regions(text, g)
                 if self.hull:
                     counts = self._hulls(text, g, counts)
-            counts_h = counts.cpu().numpy()             # the one synchronisation before the download
+                if self.flat is not None:               # the flat stage writes the page's mask; compose's, of the reduced plane, is scratch
+                    counts, split, src = self._flat(page_d, text, g, counts, mask_u8)
+                    compose_mask = torch.empty_like(mask_u8)
+            counts_h = all_h = counts.cpu().numpy()     # the one synchronisation before the download
+            flat_pixels = 0
             if self.regions:
-                packed_h = counts_h
+                packed_h = all_h[:split] if split else all_h
                 counts_h, table, found, kept, truncated = unpack_regions(packed_h, g.count, self.max_regions)
                 self.last_regions = {"table": table, "found": found, "kept": kept, "truncated": truncated}
                 if self.hull:
                     self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
+                if self.flat is not None:
+                    packed_h = all_h[split:]            # behind the hulls: the filled plane's own components; all that follows works on them
+                    counts_h, ftable, _, _, ftruncated = unpack_regions(packed_h, g.count, self.max_regions)
+                    is_flat, colour, ring_pixels = unpack_flat(packed_h, g.count, self.max_regions, len(ftable))
+                    self.last_regions["flat"] = {"table": ftable, "is_flat": is_flat, "colour": colour, "ring_pixels": ring_pixels}
+                    flat_pixels = int(ftable[is_flat, 1].sum(dtype=np.int64))
+                    table, truncated = ftable[~is_flat], ftruncated     # what pack plans its windows on
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
             windows = self._plan(table, truncated, g, len(selected)) if (self.pack and any_text) else None
             if windows is not None:
-                out, origin, rect = self._fill_windows(page_d, text, g, *windows)
+                out, origin, rect = self._fill_windows(src, text, g, *windows)
             else:
-                out, slot = self._fill(page_d, text, g, selected) if (selected and any_text) else (None, None)
-            off = (h * w * 3 + 15) // 16 * 16           # clean + mask in one buffer (one download); the kernel wants both 4-byte aligned
-            both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
-            clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
+                out, slot = self._fill(src, text, g, selected) if (selected and any_text) else (None, None)
             if windows is not None:
-                _compose_page_windows_u8(page_d, text, out, origin, rect, g, clean, mask_u8)
+                _compose_page_windows_u8(src, text, out, origin, rect, g, clean, compose_mask)
             else:
-                _compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
-        self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0, "text_pixels": int(counts_h.sum())}
+                _compose_page_u8(src, text, out, slot, g, clean, compose_mask)
+        self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0,
+                           "text_pixels": int(counts_h.sum()) + flat_pixels}
+        if self.flat is not None:
+            self.last_stats.update(flat_regions=int(is_flat.sum()), flat_pixels=flat_pixels)
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)

@@ -7,6 +7,10 @@ in place on its text plane between the mask and the tile selection (``pipeline.p
 
 ``fill_region_hulls`` is the demo's next step, ``cv2.convexHull`` + ``cv2.drawContours(..., -1)``: the convex hull of every kept region
 filled into the plane (``tsii_region_hulls``, ``csrc/hull.hip``; "K12: region hulls"), behind the same labelling.
+
+``flat_fill_regions`` is the reference README's middle step, "use the generated mask to white out words", for text on one flat colour:
+a region whose surrounding ring of page pixels is uniform within a tolerance is painted with the ring's mean colour and leaves the
+plane (``tsii_flat_regions``, ``csrc/flat.hip``; "K13: flat regions"); what is left is the text an inpainting net has to see.
 """
 from typing import NamedTuple
 
@@ -23,6 +27,18 @@ class RegionHulls(NamedTuple):
     filled: object
     regions: "TextRegions"
     hull_area: np.ndarray
+
+
+class FlatFill(NamedTuple):
+    """``painted``: uint8 ``[H, W, 3]``, the page with every flat region in its ring's mean colour.  ``rest``: uint8 ``[H, W]`` of
+    0 / 255, the text that is left for a net.  ``regions``: the ``TextRegions`` of the input.  Per table row: ``is_flat`` (numpy bool
+    ``[n]``), ``colour`` (uint8 ``[n, 3]``, the rounded mean of the ring; 0 without a ring) and ``ring_pixels`` (int32 ``[n]``)."""
+    painted: object
+    rest: object
+    regions: "TextRegions"
+    is_flat: np.ndarray
+    colour: np.ndarray
+    ring_pixels: np.ndarray
 
 
 class TextRegions(NamedTuple):
@@ -44,6 +60,13 @@ def check_region_args(connectivity, min_area, max_regions):
         raise ValueError(f"min_area {min_area} must be an integer >= 0")
     if int(max_regions) != max_regions or max_regions < 1:
         raise ValueError(f"max_regions {max_regions} must be an integer >= 1")
+
+
+def check_flat_args(tol, ring):
+    if isinstance(tol, bool) or int(tol) != tol or not 0 <= tol <= 255:
+        raise ValueError(f"flat tolerance {tol} must be an integer 0..255")
+    if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 8:
+        raise ValueError(f"flat ring {ring} must be an integer 1..8")
 
 
 def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
@@ -81,6 +104,34 @@ def _region_hulls(text, labels, packed, max_regions, grid=None):
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
     call("tsii_region_hulls", ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, tile, halo,
          ptr(packed[:nt]) if nt else None, ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+
+
+def _flat_regions(page, text, labels, packed, max_regions, ring, tol, painted, mask=None, grid=None):
+    """``tsii_flat_regions`` in place on the device plane ``text``, behind the ``_text_regions`` call that labelled THIS plane (same
+    ``grid``): ``packed`` is that call's tensor with a tail of ``5 * max_regions`` words right behind the table,
+    ``[core counts | found, kept | table | flat rows]``; the core counts at its front are rewritten for the reduced plane.  ``painted``
+    (and ``mask``, the 0 / 255 plane of the text on entry) are written."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    nt = 0 if grid is None else grid.count
+    n = int(max_regions)
+    assert packed.numel() == nt + 2 + 11 * n and packed.dtype == torch.int32 and packed.device == text.device
+    assert page.shape == (h, w, 3) and painted.shape == (h, w, 3) and all(t.dtype == torch.uint8 and t.is_contiguous() for t in (page, painted))
+    assert mask is None or (mask.shape == (h, w) and mask.dtype == torch.uint8 and mask.is_contiguous())
+    nbytes = int(_lib.lib().tsii_flat_regions_ws_bytes(h, w, n))
+    if nbytes == 0:
+        raise ValueError(f"text plane of {h} x {w} pixels is out of range")
+    ws = ops._ws(nbytes, text)
+    tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
+    call("tsii_flat_regions", ptr(page), ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, int(ring), int(tol),
+         tile, halo, ptr(packed[:nt]) if nt else None, ptr(painted), ptr(mask), ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+
+
+def unpack_flat(packed_h, nt, max_regions, n):
+    """host copy of a ``packed`` with flat rows -> (is_flat bool ``[n]``, colour uint8 ``[n, 3]``, ring_pixels int32 ``[n]``) of the ``n``
+    table rows in use"""
+    at = nt + 2 + 6 * int(max_regions)
+    rows = packed_h[at:at + 5 * n].reshape(n, 5)
+    return rows[:, 0] != 0, rows[:, 1:4].astype(np.uint8), rows[:, 4].copy()
 
 
 def unpack_hull_area(packed_h, nt, max_regions, n):
@@ -125,6 +176,32 @@ def fill_region_hulls(text, connectivity=8, min_area=0, max_regions=4096, device
     _, table, found, kept, truncated = unpack_regions(packed_h, 0, max_regions)
     hull_area = unpack_hull_area(packed_h, 0, max_regions, len(table))
     return RegionHulls(_like(plane * 255, text), TextRegions(_like(labels, text), table, found, kept, truncated), hull_area)
+
+
+def flat_fill_regions(page_u8, mask_u8, tol, ring=3, connectivity=8, min_area=0, max_regions=4096, device=None) -> FlatFill:
+    """Paint the text that sits on one flat colour.  ``page_u8``: ``[H, W, 3]`` uint8; ``mask_u8``: ``[H, W]`` uint8, non-zero = text (the
+    255 masks ``TextEraser`` returns work directly); numpy or torch, host or device, neither is modified.  Regions below ``min_area`` are
+    dropped first, as in ``text_regions``.  A kept region is FLAT when the page pixels within ``ring`` (1..8, Chebyshev distance) of it
+    that are not text themselves differ by at most ``tol`` (0..255) grey levels in every channel; it is painted with their rounded mean
+    colour and leaves ``rest``.  Regions without a ring, and kept regions beyond ``max_regions``, are never flat.  ``painted`` comes
+    back the same kind and on the same device as ``page_u8``, ``rest`` and the labels as ``mask_u8``; one synchronisation (the read-back
+    of the counts, the table and the flat rows).  Host arguments are computed on ``device`` (default ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_flat_args(tol, ring)
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
+        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
+    plane = _plane_on_device(mask_u8, device)
+    page = p.to(plane.device).contiguous()
+    n = int(max_regions)
+    labels, packed = _text_regions(plane, connectivity, min_area, n, tail=5 * n)
+    painted = torch.empty_like(page)
+    _flat_regions(page, plane, labels, packed, n, ring, tol, painted)
+    packed_h = packed.cpu().numpy()
+    _, table, found, kept, truncated = unpack_regions(packed_h, 0, n)
+    is_flat, colour, ring_pixels = unpack_flat(packed_h, 0, n, len(table))
+    return FlatFill(_like(painted, page_u8), _like(plane * 255, mask_u8), TextRegions(_like(labels, mask_u8), table, found, kept, truncated),
+                    is_flat, colour, ring_pixels)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

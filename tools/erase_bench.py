@@ -3,6 +3,7 @@
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
                                 [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
+                                [--bubbles SHARE] [--flat T [--flat-ring N]]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -28,6 +29,11 @@ the host clock (``plan_host_ms``, behind the read-back, so nothing else is in fl
 tiles the stages ``page_tiles_fill`` / ``compose_page_u8`` are replaced by ``page_windows_fill`` / ``compose_page_windows_u8``
 (tsii_page_windows_fill, tsii_compose_page_windows_u8); ``filler_tiles`` reports both counts.  Compare with a run without ``--pack`` in
 the same session (same ``--min-area``).
+``--bubbles SHARE`` replaces the page by a noisy one on which the first SHARE (0..1) of the blobs of the same blob field each sit on a
+disc of one colour, as lettering sits in a speech bubble; ``--flat T`` (turns the regions stage on) adds the ``flat`` stage
+(tsii_flat_regions, behind the regions / hulls stages; behind the hulls with the second labelling it needs, which is timed with it) and
+sends the filler only what is left.  ``regions`` then reports ``flat_regions`` / ``flat_pixels`` and ``labelled`` (the components the
+stage worked on).  Compare with a run on the same ``--bubbles`` page without ``--flat`` in the same session.
 """
 import argparse
 import json
@@ -44,8 +50,8 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 
-def blob_field(h, w, fraction, seed):
-    """logits [h, w] of a page whose text is rectangular blobs covering about ``fraction`` of it"""
+def blob_field(h, w, fraction, seed, rects=None):
+    """logits [h, w] of a page whose text is rectangular blobs covering about ``fraction`` of it (``rects``: a list that gets the blobs)"""
     rng = np.random.default_rng(seed)
     page = np.full((h, w), -4.0, np.float32)
     target, covered = fraction * h * w, 0
@@ -54,6 +60,20 @@ def blob_field(h, w, fraction, seed):
         y, x = int(rng.integers(0, max(1, h - bh))), int(rng.integers(0, max(1, w - bw)))
         page[y:y + bh, x:x + bw] = 4.0
         covered += bh * bw
+        if rects is not None:
+            rects.append((y, x, bh, bw))
+    return page
+
+
+def bubble_page(h, w, rects, share, seed, margin=16):
+    """a noisy page; the first ``share`` of the blobs ``rects`` each on an ellipse of one colour that reaches ``margin`` pixels beyond the
+    blob's corners (later bubbles may cut into earlier ones, blobs may touch: the share of FLAT regions is what the run reports)"""
+    rng = np.random.default_rng(seed)
+    page = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
+    yy, xx = np.mgrid[0:h, 0:w]
+    for y, x, bh, bw in rects[:int(round(share * len(rects)))]:
+        ry, rx = (bh / 2 + margin) * 1.42, (bw / 2 + margin) * 1.42
+        page[((yy - (y + bh / 2)) / ry) ** 2 + ((xx - (x + bw / 2)) / rx) ** 2 <= 1.0] = rng.integers(180, 256, size=3, dtype=np.uint8)
     return page
 
 
@@ -84,6 +104,9 @@ def main(argv=None):
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
     ap.add_argument("--pack", action="store_true", help="windows on the text regions instead of the grid's tiles (turns the regions stage on)")
+    ap.add_argument("--bubbles", type=float, default=None, metavar="SHARE", help="a noisy page with this share of the blobs on discs of one colour")
+    ap.add_argument("--flat", type=int, default=None, metavar="T", help="time the flat stage (tsii_flat_regions) with this tolerance")
+    ap.add_argument("--flat-ring", type=int, default=3)
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
@@ -100,18 +123,23 @@ def main(argv=None):
     if (hs, ws) != (h, w):
         gs = P.tile_grid(hs, ws, args.tile, args.halo)
     with_seg = gs is not g
-    field = blob_field(h, w, 0.0 if args.all_text else args.text_fraction, 1)
+    rects = []
+    field = blob_field(h, w, 0.0 if args.all_text else args.text_fraction, 1, rects)
+    if args.bubbles is not None:
+        page = bubble_page(h, w, rects, args.bubbles, 2)
     if args.all_text:
         field.fill(4.0)
     if with_seg:                                          # the same text, sampled at the working size
         field = F.interpolate(torch.from_numpy(field)[None, None], size=(hs, ws), mode="nearest")[0, 0].numpy()
     logits_fixed = tile_logits(field, gs, dev)
-    with_regions = args.min_area > 0 or args.hull or args.pack
+    with_flat = args.flat is not None
+    with_regions = args.min_area > 0 or args.hull or args.pack or with_flat
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
-                          max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select)
+                          max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
+                          flat=args.flat, flat_ring=args.flat_ring)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -123,12 +151,14 @@ def main(argv=None):
         stages.append("regions")                            # timed with its own pair of events, between the mask and the read-back
     if args.hull:
         stages.append("hulls")                              # its own pair of events, right behind the regions stage
+    if with_flat:
+        stages.append("flat")                               # its own pair of events, behind the regions / hulls stages
     if with_seg:
         stages += ["resize", "plane_up"]                    # their own pairs of events: behind the upload / behind the mask
 
     def one_page():
         marks = [ev() for _ in range(11)]
-        reg0, reg1, hul1, res1, up0, up1 = ev(), ev(), ev(), ev(), ev(), ev()
+        reg0, reg1, hul1, res1, up0, up1, fl0, fl1 = ev(), ev(), ev(), ev(), ev(), ev(), ev(), ev()
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
@@ -157,8 +187,14 @@ def main(argv=None):
                 if args.hull:
                     counts = eraser._hulls(text, g, counts)
                     hul1.record()
+            src, split = page_d, 0                          # src: the page the filler and compose see
+            if with_flat:
+                page_mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
+                fl0.record()
+                counts, split, src = eraser._flat(page_d, text, g, counts, page_mask)
+                fl1.record()
             marks[4].record()
-            counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table)
+            counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table + flat rows)
             marks[5].record()
             d2h_words = int(counts_h.size)
             region_info = None
@@ -167,7 +203,15 @@ def main(argv=None):
                 counts_h, table, found, kept, truncated = RG.unpack_regions(packed_h, g.count, args.max_regions)
                 region_info = {"found": found, "kept": kept, "truncated": truncated}
                 if args.hull:
-                    region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h, g.count, args.max_regions, len(table)).sum(dtype=np.int64))
+                    region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h[:split] if split else packed_h, g.count, args.max_regions,
+                                                                         len(table)).sum(dtype=np.int64))
+                if with_flat:                               # everything behind works on the flat stage's own components and counts
+                    own = packed_h[split:]
+                    counts_h, ftable, _, _, truncated = RG.unpack_regions(own, g.count, args.max_regions)
+                    is_flat = RG.unpack_flat(own, g.count, args.max_regions, len(ftable))[0]
+                    region_info.update(labelled=len(ftable), flat_regions=int(is_flat.sum()),
+                                       flat_pixels=int(ftable[is_flat, 1].sum(dtype=np.int64)))
+                    table = ftable[~is_flat]
             selected = [t for t in range(g.count) if counts_h[t] > 0]
             windows, plan_ms = None, 0.0
             if args.pack:
@@ -184,18 +228,21 @@ def main(argv=None):
                 slot = torch.from_numpy(slot_h).to(dev)
                 n_fill = len(selected)
             marks[10].record()                              # the two small uploads above belong to no stage
-            img, mplane = P._page_windows_fill(page_d, text, g, origin) if windows is not None else P._page_tiles_fill(page_d, text, g, ids)
+            if n_fill:
+                img, mplane = P._page_windows_fill(src, text, g, origin) if windows is not None else P._page_tiles_fill(src, text, g, ids)
             marks[6].record()
-            xi = img.permute(0, 3, 1, 2)
-            outs = [P.to_nhwc(fil((xi[b:b + args.tile_batch], P.MaskParts.from_plane(mplane[b:b + args.tile_batch], 3))))
-                    for b in range(0, n_fill, args.tile_batch)]
-            out = outs[0] if len(outs) == 1 else torch.cat(outs)
+            out = None                                      # a page whose text is all flat: the filler is not called
+            if n_fill:
+                xi = img.permute(0, 3, 1, 2)
+                outs = [P.to_nhwc(fil((xi[b:b + args.tile_batch], P.MaskParts.from_plane(mplane[b:b + args.tile_batch], 3))))
+                        for b in range(0, n_fill, args.tile_batch)]
+                out = outs[0] if len(outs) == 1 else torch.cat(outs)
             marks[7].record()
             clean, mask_u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev), torch.empty((h, w), dtype=torch.uint8, device=dev)
             if windows is not None:
-                P._compose_page_windows_u8(page_d, text, out, origin, rect, g, clean, mask_u8)
+                P._compose_page_windows_u8(src, text, out, origin, rect, g, clean, mask_u8)
             else:
-                P._compose_page_u8(page_d, text, out, slot, g, clean, mask_u8)
+                P._compose_page_u8(src, text, out, slot if out is not None else None, g, clean, mask_u8)
             marks[8].record()
             clean.cpu(), mask_u8.cpu()
             marks[9].record()
@@ -207,6 +254,8 @@ def main(argv=None):
             t.append(reg0.elapsed_time(reg1))
         if args.hull:
             t.append(reg1.elapsed_time(hul1))
+        if with_flat:
+            t.append(fl0.elapsed_time(fl1))
         if with_seg:
             t[1] = res1.elapsed_time(marks[2])
             t[3] = marks[3].elapsed_time(up0)
@@ -239,6 +288,9 @@ def main(argv=None):
         bytes_["regions"] = 18 * npx        # local 1 + 4, measure 4, filter 4 + 4 + 1 ("text regions"); seams and statistics on top
     if args.hull:
         bytes_["hulls"] = 5 * npx + n_text  # extents 4 (labels), finish 1, the fill's stores at most once per final text pixel ("region hulls")
+    if with_flat:                           # DESIGN.md, "flat regions": ring 1 (text) + apron, apply 3 + 1 in, 3 + 1 + 1 out, labels on the text
+        apron = (64 + 2 * args.flat_ring) * (32 + 2 * args.flat_ring) / 2048.0
+        bytes_["flat"] = int(apron * npx) + 9 * npx + 8 * int(runs[0][5]["flat_pixels"] + n_text) + (18 * npx if args.hull else 0)
 
     def timed(fn, sync=True):
         for _ in range(args.warmup):
@@ -355,6 +407,7 @@ def main(argv=None):
         # the stages that copy to the host before the download: still one, whatever it carries
         "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
         "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
+        "bubbles": args.bubbles, "flat": args.flat, "flat_ring": args.flat_ring if with_flat else None,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
