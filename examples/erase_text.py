@@ -16,6 +16,9 @@ the scale it was trained at; the resize and the way back of the mask run on the 
 text block is then inpainted whole, in the middle of one window.
 ``--flat T`` (0..255) paints the text regions whose surroundings (``--flat-ring N`` pixels around them, default 3) are of one colour within
 T grey levels -- lettering in a speech bubble -- with that colour on the device; only the text over artwork goes to the inpainting net.
+``--filler harmonic`` needs no inpainting checkpoint: the holes take the smooth continuation of their surroundings (``T.HarmonicFill``,
+``--sweeps N`` Jacobi sweeps per level, default 8), the right fill for text on a gradient, a soft shadow or a sky; no inpainting net is
+built or loaded.
 """
 import argparse
 import os
@@ -64,12 +67,17 @@ def main(argv=None):
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
     ap.add_argument("--flat", type=int, default=None, metavar="T", help="paint text regions whose surroundings are uniform within T grey levels")
     ap.add_argument("--flat-ring", type=int, default=3, metavar="N", help="width of the ring of surrounding pixels --flat looks at (1..8)")
+    ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: fill the holes with T.HarmonicFill, without an inpainting net")
+    ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     nets = []
     for name, ckpt in ((args.seg_model, args.seg_checkpoint), (args.fill_model, args.fill_checkpoint)):
+        if len(nets) == 1 and args.filler == "harmonic":
+            nets.append(T.HarmonicFill(args.sweeps))                       # a kernel, not a net: nothing to build or load
+            break
         net = getattr(T, name)()
         if ckpt:
             net.load_state_dict(torch.load(ckpt, map_location="cpu"))      # the tolerant loader: reports and skips what does not fit

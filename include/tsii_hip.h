@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 12
+#define TSII_ABI_VERSION 13
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -763,6 +763,32 @@ size_t tsii_flat_regions_ws_bytes(int h, int w, int max_regions);
 int tsii_flat_regions(const uint8_t* page, uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
                       int max_regions, int ring, int tol, int tile, int halo, int* core_count, uint8_t* painted, uint8_t* mask,
                       int* flat, void* ws, void* stream);
+
+/* ---- K14: harmonic fill (csrc/harmonic.hip) -- a filler that is a kernel and not a net: the holes of an image are filled with the smooth
+ * continuation of the pixels around them (Laplace's equation over the holes, the valid pixels as the boundary), in ONE coarse-to-fine
+ * pass.  Per image; the 3 channels share one validity plane.
+ * Inputs: x fp32 NHWC [n,h,w,3]; mask fp32 [n,h,w], a pixel is VALID iff mask != 0 (the plane tsii_page_tiles_fill writes: 1 = keep,
+ * 0 = hole); sweeps 0..16.  Output: out fp32 NHWC [n,h,w,3], never x itself.  The value of x at a hole pixel is NEVER USED (it may be NaN
+ * or Inf): values are selected by validity, not multiplied by the mask.
+ *   1. Levels.  Level 0 is the image: v_0 = x on valid pixels, m_0 = valid.  Level l+1 has ceil(h_l / 2) x ceil(w_l / 2) pixels; the
+ *      children of its pixel (i, j) are the level-l pixels (2i..2i+1, 2j..2j+1) that exist (2 or 1 at an odd edge); m_{l+1} = any child
+ *      valid, v_{l+1} = the mean of the VALID children.  Level L is the 1 x 1 level.
+ *   2. Apex.  u_L = v_L if m_L, else 0: an image without a valid pixel comes back as zeros.
+ *   3. Coarse to fine, l = L-1 .. 0: u_l = v_l on the pixels valid at level l and u_{l+1}(i / 2, j / 2) (the relaxed parent, nearest) on
+ *      the others; then `sweeps` Jacobi sweeps: in each, every pixel that is a HOLE at level l becomes the mean of its in-bounds
+ *      4-neighbours' values from before the sweep (2, 3 or 4 of them on a level of two pixels a side or more, 1 or 2 on a level one
+ *      pixel wide; nothing mirrored).  Valid pixels never change.
+ *   4. out = u_0; on valid pixels out equals x bit for bit.
+ * Every hole value is a convex combination of valid inputs.  Every mean adds its terms in one fixed order (children: row by row; neighbours:
+ * up, down, left, right) and divides by their count: the result does not depend on how the work is cut into blocks, an image of a batch
+ * equals the same image run alone, two runs give the same bits.  No atomics.
+ * No allocation, no host synchronisation, everything on the caller's stream.
+ * ws: tsii_harmonic_fill_ws_bytes(n, h, w) bytes (0: geometry refused; the coarse levels' values and validity bytes, about 0.36 of x),
+ * 4-byte aligned (16 for the vector paths); needs nothing cleared beforehand and holds nothing a later call depends on.
+ * Refused (non-zero return, tsii_last_error, nothing launched): n, h or w < 1; n*h*w*3 > 2^31; sweeps outside 0..16; a NULL among x, mask,
+ * out, ws; out == x. */
+size_t tsii_harmonic_fill_ws_bytes(int n, int h, int w);
+int tsii_harmonic_fill(const float* x, const float* mask, int n, int h, int w, int sweeps, float* out, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,115 @@
+"""A filler that is a kernel and not a net: the harmonic fill of ``csrc/harmonic.hip`` (include/tsii_hip.h, "K14: harmonic fill").
+
+The holes of an image are filled with the smooth continuation of the pixels around them -- Laplace's equation over the holes with the
+valid pixels as the boundary, in one coarse-to-fine pass on the device: a pyramid of means of the valid pixels, then, level by level
+back down, every hole starts from its relaxed parent and takes ``sweeps`` Jacobi sweeps.  It is the right fill for text on a smooth
+background (a gradient, a soft shadow, a sky) and needs no inpainting checkpoint:
+
+    eraser = T.TextEraser(T.XceptionTextSegment().cuda(), T.HarmonicFill())
+
+``HarmonicFill`` obeys the ``filler`` calling convention of ``TextEraser``; ``harmonic_fill`` is the stand-alone form for a uint8 page
+and a mask.  Device tensors only: there is no CPU path.
+"""
+import numpy as np
+import torch
+
+from . import _lib, ops
+from ._lib import call, ptr
+from .masks import MaskParts
+
+MAX_SWEEPS = 16                 # what tsii_harmonic_fill accepts (the LDS a block has for its patch and apron)
+
+
+def check_sweeps(sweeps):
+    if isinstance(sweeps, bool) or int(sweeps) != sweeps or not 0 <= sweeps <= MAX_SWEEPS:
+        raise ValueError(f"sweeps {sweeps} must be an integer in 0..{MAX_SWEEPS}")
+    return int(sweeps)
+
+
+def _harmonic_fill(x_nhwc, plane, sweeps):
+    """fp32 NHWC ``[n, h, w, 3]`` and its validity plane fp32 ``[n, h, w]`` (valid iff != 0) -> the filled fp32 NHWC tensor
+    (``tsii_harmonic_fill``); what ``x_nhwc`` holds under a hole is never read"""
+    n, h, w, c = (int(v) for v in x_nhwc.shape)
+    assert c == 3 and tuple(plane.shape) == (n, h, w)
+    _lib.check_device(x_nhwc, plane)
+    assert x_nhwc.device == plane.device and x_nhwc.is_contiguous() and plane.is_contiguous()
+    nbytes = int(_lib.lib().tsii_harmonic_fill_ws_bytes(n, h, w))
+    if nbytes == 0:
+        raise ValueError(f"harmonic fill: {n} images of {h} x {w} pixels (every extent >= 1, at most 2^31 elements)")
+    out = torch.empty_like(x_nhwc)
+    ws = ops._ws(nbytes, x_nhwc)
+    call("tsii_harmonic_fill", ptr(x_nhwc), ptr(plane), n, h, w, int(sweeps), ptr(out), ptr(ws), _lib.stream())
+    return out
+
+
+def _validity_plane(mask, n, h, w):
+    """one fp32 plane ``[n, h, w]`` from a ``MaskParts`` of one planar part, a tensor ``[N,1,H,W]`` / ``[N,3,H,W]`` with equal
+    channels, or a plane ``[N,H,W]``"""
+    if isinstance(mask, torch.Tensor) and mask.dim() == 3:
+        plane = mask
+    else:
+        if isinstance(mask, torch.Tensor):
+            if mask.dim() != 4 or mask.shape[1] not in (1, 3):
+                raise ValueError(f"mask must be [N,1,H,W], [N,3,H,W] with equal channels or [N,H,W], got {tuple(mask.shape)}")
+            mask = MaskParts.from_tensor(mask)
+        if not isinstance(mask, MaskParts) or len(mask.parts) != 1:
+            raise ValueError("mask must be a MaskParts of one part, a tensor [N,1,H,W] / [N,3,H,W] or a plane [N,H,W]")
+        part = mask.parts[0]
+        if part.planar:
+            plane = part.plane
+        else:                                           # a materialised [N,H,W,C] mask: one plane only if its channels agree
+            full = part.full
+            if not bool((full == full[..., :1]).all()):
+                raise ValueError("harmonic fill: the 3 channels share one validity plane; a per-channel mask is refused")
+            plane = full[..., 0]
+    if tuple(plane.shape) != (n, h, w):
+        raise ValueError(f"mask plane {tuple(plane.shape)} for {n} images of {h} x {w}")
+    return plane.float().contiguous()
+
+
+class HarmonicFill:
+    """``out[N,3,H,W] = HarmonicFill(sweeps=8)((x[N,3,H,W], mask))``: the ``filler`` of a ``TextEraser`` without a net.  ``mask`` is 1
+    (non-zero) where ``x`` is valid and 0 over the holes: a ``MaskParts`` of one planar part (what ``TextEraser`` passes), a tensor
+    ``[N,1,H,W]`` or ``[N,3,H,W]`` with equal channels, or a plane ``[N,H,W]``.  A channels-last ``x`` is used without a copy; the
+    result is the NCHW-shaped view of the NHWC output.  Valid pixels come back bit for bit; what ``x`` holds under a hole is never
+    read.  ``sweeps`` (0..16) Jacobi sweeps per level: 8 puts interior holes of a smooth page within one grey level of the exact
+    harmonic solution.  Not an ``nn.Module``: no parameters, nothing to load."""
+
+    def __init__(self, sweeps=8):
+        self.sweeps = check_sweeps(sweeps)
+
+    def __call__(self, args):
+        x, mask = args
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"x must be [N,3,H,W], got {tuple(getattr(x, 'shape', ()))}")
+        n, _, h, w = (int(v) for v in x.shape)
+        plane = _validity_plane(mask, n, h, w)
+        out = _harmonic_fill(x.float().permute(0, 2, 3, 1).contiguous(), plane, self.sweeps)
+        return out.permute(0, 3, 1, 2)
+
+    def __repr__(self):
+        return f"HarmonicFill(sweeps={self.sweeps})"
+
+
+def harmonic_fill(page_u8, mask_u8, sweeps=8, device=None):
+    """``clean_u8``: the page with the pixels under the mask replaced by the harmonic fill of their surroundings.  ``page_u8``:
+    ``[H, W, 3]`` uint8 of any size; ``mask_u8``: ``[H, W]`` uint8, non-zero = remove (the 255 masks ``TextEraser`` returns work
+    directly); numpy or torch, neither is modified.  One call of the kernel on the whole page.  Pixels outside the mask come back byte
+    for byte; inside, ``floor(clamp(v, 0, 1) * 255 + 0.5)`` of the filled value, the compose kernels' rounding.  The result is the same
+    kind (and on the same device) as ``page_u8``; host arguments are computed on ``device`` (default ``cuda:0``)."""
+    sweeps = check_sweeps(sweeps)
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    m = torch.from_numpy(np.ascontiguousarray(mask_u8)) if isinstance(mask_u8, np.ndarray) else mask_u8
+    if p.dim() != 3 or p.shape[2] != 3 or p.dtype != torch.uint8 or p.shape[0] < 1 or p.shape[1] < 1:
+        raise ValueError(f"page must be [H, W, 3] uint8, got {tuple(p.shape)} {p.dtype}")
+    if m.dtype != torch.uint8 or tuple(m.shape) != tuple(p.shape[:2]):
+        raise ValueError(f"mask must be [H, W] uint8 for a page of {tuple(p.shape)}, got {tuple(m.shape)} {m.dtype}")
+    dev = torch.device(device) if device is not None else (p.device if p.is_cuda else torch.device("cuda:0"))
+    page, hole = p.to(dev).contiguous(), m.to(dev) != 0
+    x = (page.float() / 255.0).unsqueeze(0)
+    filled = _harmonic_fill(x, (~hole).float().unsqueeze(0), sweeps)[0]
+    rounded = torch.floor(filled.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+    clean = torch.where(hole.unsqueeze(-1), rounded, page)
+    if isinstance(page_u8, np.ndarray):
+        return clean.cpu().numpy()
+    return clean if clean.device == page_u8.device else clean.to(page_u8.device)

@@ -107,6 +107,8 @@ def main(argv=None):
     ap.add_argument("--bubbles", type=float, default=None, metavar="SHARE", help="a noisy page with this share of the blobs on discs of one colour")
     ap.add_argument("--flat", type=int, default=None, metavar="T", help="time the flat stage (tsii_flat_regions) with this tolerance")
     ap.add_argument("--flat-ring", type=int, default=3)
+    ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
+    ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
@@ -115,7 +117,8 @@ def main(argv=None):
     assert torch.cuda.is_available(), "erase_bench needs an MI355X"
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
-    seg, fil = getattr(T, args.seg_model)().to(dev).eval(), getattr(T, args.fill_model)().to(dev).eval()
+    seg = getattr(T, args.seg_model)().to(dev).eval()
+    fil = T.HarmonicFill(args.sweeps) if args.filler == "harmonic" else getattr(T, args.fill_model)().to(dev).eval()
     h, w = args.size
     page = np.ascontiguousarray((manga_tile(max(h, w), np.random.default_rng(0)).transpose(1, 2, 0)[:h, :w] * 255).astype(np.uint8))
     g = gs = P.tile_grid(h, w, args.tile, args.halo)      # gs: the segmenter's grid
@@ -396,7 +399,8 @@ def main(argv=None):
 
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
-        "seg_model": args.seg_model, "fill_model": args.fill_model, "tiles": g.count, "selected_tiles": n_sel,
+        "seg_model": args.seg_model, "fill_model": repr(fil) if args.filler == "harmonic" else args.fill_model, "filler": args.filler,
+        "sweeps": args.sweeps if args.filler == "harmonic" else None, "tiles": g.count, "selected_tiles": n_sel,
         "seg_long_side": args.seg_long_side, "seg_size": [hs, ws], "seg_tiles": gs.count, "host_route_resample": host_resample,
         "text_fraction": round(n_text / npx, 4), "repeats": args.repeats, "warmup": args.warmup,
         "stage_ms": {s: {"median": round(med[s], 4), "min": round(min(v), 4), "max": round(max(v), 4)} for s, v in ms.items()},
