@@ -1325,18 +1325,35 @@ def test_batchnorm_apply_and_backward_kernels_row_tails(emu, m, c, act, slope):
     passes would otherwise only show up as 'noise' in whole-network gradient tests."""
     L = emu
     rng = np.random.default_rng(m * 131 + c * 7 + act)
-    y = (rng.standard_normal((m, c)) * 1.5 + 0.3).astype(np.float32)
     res = rng.standard_normal((m, c)).astype(np.float32)
     dout = rng.standard_normal((m, c)).astype(np.float32)
-    gamma = rng.uniform(0.5, 1.5, size=c).astype(np.float32)
-    beta = (rng.standard_normal(c) * 0.3).astype(np.float32)
     eps = 1e-5
+    # mean / var are arguments of the entry points and the backward formulas are plain formulas in them: they are DRAWN (a few
+    # variances near 0, gammas of either sign), the pre-activations z are drawn at least 2^-10 away from the kinks 0 and 6, and y is
+    # solved from them -- no element sits where an fp32 z could take the other derivative, so nothing is left out of a comparison
+    mean = rng.standard_normal(c).astype(np.float32)
+    var = rng.uniform(0.5, 4.0, size=c).astype(np.float32)
+    var[3::11] = rng.uniform(1e-4, 1e-3, size=len(var[3::11]))
+    gamma = (rng.uniform(0.5, 1.5, size=c) * rng.choice([-1.0, 1.0], size=c)).astype(np.float32)
+    beta = (rng.standard_normal(c) * 0.3).astype(np.float32)
+    beta[0] = 0.0
+    zt = 1.0 + 3.0 * rng.standard_normal((m, c))
+    zt = np.where(np.abs(zt) < 2.0 ** -10, np.copysign(1.5 * 2.0 ** -10, zt), zt)
+    zt = np.where(np.abs(zt - 6.0) < 2.0 ** -10, 6.0 + np.copysign(1.5 * 2.0 ** -10, zt - 6.0), zt)
+    y = (mean.astype(np.float64) + (zt - beta) / gamma * np.sqrt(var.astype(np.float64) + np.float32(eps))).astype(np.float32)
+    # exact kinks, planted: channel 0 has beta == 0 and y == mean in >= 5 % of its rows, so z == 0 in any arithmetic (ReLU and ReLU6
+    # pass 0 there, LeakyReLU its slope -- what act_grad documents and _act_np restates)
+    planted = np.zeros(m, bool)
+    planted[rng.choice(m, max(1, -(-6 * m // 100)), replace=False)] = True
+    y[planted, 0] = mean[0]
     y64 = y.astype(np.float64)
-    mean = y64.mean(0).astype(np.float32) if m > 1 else y64[0].astype(np.float32)
-    var = (y64.var(0) if m > 1 else np.ones(c)).astype(np.float32)
-    rstd = 1.0 / np.sqrt(var.astype(np.float64) + eps)
+    rstd = 1.0 / np.sqrt(var.astype(np.float64) + np.float32(eps))
     xhat = (y64 - mean.astype(np.float64)) * rstd
     z = xhat * gamma + beta
+    gap = np.minimum(np.abs(z), np.abs(z - 6.0))
+    assert np.all(z[planted, 0] == 0.0)
+    gap[planted, 0] = np.inf
+    assert (gap < 2.0 ** -11).sum() == 0
     # ---- forward apply, with and without the residual
     for with_res in (False, True):
         out = np.full((m, c), np.nan, np.float32)
@@ -1346,8 +1363,6 @@ def test_batchnorm_apply_and_backward_kernels_row_tails(emu, m, c, act, slope):
         assert np.isfinite(out).all() and np.abs(out - ref).max() <= 2e-6 * max(1.0, np.abs(ref).max()), (with_res, np.abs(out - ref).max())
     # ---- backward: training (batch statistics) and eval
     a, dadz = _act_np(z, act, slope)
-    # keep the comparison away from the activation kinks: an fp32 z within rounding of a kink legitimately takes either derivative
-    safe = np.ones_like(z, bool) if act == 0 else (np.abs(z) > 1e-4) & ((np.abs(z - 6) > 1e-4) if act == 3 else True)
     dz = dout.astype(np.float64) * dadz
     dbeta_r, dgamma_r = dz.sum(0), (dz * xhat).sum(0)
     dy_train = (dz - dbeta_r / m - xhat * dgamma_r / m) * gamma * rstd
@@ -1357,12 +1372,9 @@ def test_batchnorm_apply_and_backward_kernels_row_tails(emu, m, c, act, slope):
         dy = np.full((m, c), np.nan, np.float32); dg = np.full(c, np.nan, np.float32); db = np.full(c, np.nan, np.float32)
         ws = WS(nb)
         assert L.tsii_bn_act_bwd(P(dout), P(y), m, c, P(mean), P(var), P(gamma), P(beta), eps, act, slope, training, P(dy), P(dg), P(db), P(ws), nb, None) == 0, L.tsii_last_error()
-        if safe.all():
-            scale = max(1.0, np.abs(dy_r).max())
-            assert np.abs(dy - dy_r).max() <= 2e-5 * scale, (training, np.abs(dy - dy_r).max())
-            assert np.abs(dg - dgamma_r).max() <= 2e-5 * max(1.0, np.abs(dgamma_r).max()) and np.abs(db - dbeta_r).max() <= 2e-5 * max(1.0, np.abs(dbeta_r).max())
-        else:
-            assert np.isfinite(dy).all()
+        scale = max(1.0, np.abs(dy_r).max())
+        assert np.abs(dy - dy_r).max() <= 2e-5 * scale, (training, np.abs(dy - dy_r).max())
+        assert np.abs(dg - dgamma_r).max() <= 2e-5 * max(1.0, np.abs(dgamma_r).max()) and np.abs(db - dbeta_r).max() <= 2e-5 * max(1.0, np.abs(dbeta_r).max())
     # ---- the 3-pass form fed with reductions somebody else took (K6c): partial rows that sum to the exact totals
     rows = 3
     part = np.zeros((rows, 2, c), np.float32)
@@ -1373,9 +1385,8 @@ def test_batchnorm_apply_and_backward_kernels_row_tails(emu, m, c, act, slope):
     ws = WS(nb)
     assert L.tsii_bn_act_bwd_pre(P(dout), P(y), m, c, P(mean), P(var), P(gamma), P(beta), eps, act, slope, 1, P(part), rows,
                                  P(dy), P(dg), P(db), P(ws), nb, None) == 0, L.tsii_last_error()
-    if safe.all():
-        assert np.abs(dy - dy_train).max() <= 5e-5 * max(1.0, np.abs(dy_train).max())
-        assert np.abs(dg - dgamma_r).max() <= 5e-5 * max(1.0, np.abs(dgamma_r).max()) and np.abs(db - dbeta_r).max() <= 5e-5 * max(1.0, np.abs(dbeta_r).max())
+    assert np.abs(dy - dy_train).max() <= 5e-5 * max(1.0, np.abs(dy_train).max())
+    assert np.abs(dg - dgamma_r).max() <= 5e-5 * max(1.0, np.abs(dgamma_r).max()) and np.abs(db - dbeta_r).max() <= 5e-5 * max(1.0, np.abs(dbeta_r).max())
 
 
 @pytest.mark.parametrize("n,hw,c", [(2, 37, 128), (1, 300, 48), (2, 64, 320), (1, 50, 32), (3, 1000, 192), (1, 20, 640), (1, 9, 2052), (1, 33, 6)])
