@@ -10,6 +10,9 @@ Writes ``<name>_clean.png`` and ``<name>_mask.png`` (255 = text) per page; ``--s
 ``--min-area N`` drops the connected text regions of fewer than N pixels on the device before anything is inpainted; ``--boxes`` also
 writes ``<name>_boxes.png``, the page with the boxes of the kept regions outlined.  ``--hull`` fills the convex hull of every kept region
 into the mask on the device (the reference demo's ``cv2.convexHull`` step), so that the inpainting net gets one solid hole per text block.
+``--group G`` groups the regions that lie within G pixels of one another into blocks on the device first (a G of about the line spacing
+makes a speech bubble's lettering one block): ``--min-area``, ``--hull``, ``--flat`` and ``--pack`` then work per block and ``--boxes``
+outlines the blocks, the boxes a translation would be typeset into.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 ``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
@@ -67,6 +70,8 @@ def main(argv=None):
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
     ap.add_argument("--flat", type=int, default=None, metavar="T", help="paint text regions whose surroundings are uniform within T grey levels")
     ap.add_argument("--flat-ring", type=int, default=3, metavar="N", help="width of the ring of surrounding pixels --flat looks at (1..8)")
+    ap.add_argument("--group", type=int, default=None, metavar="G", help="group text regions within G pixels (1..64) into blocks: --min-area, --hull, "
+                    "--flat and --pack then work per block, --boxes draws the block boxes")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: fill the holes with T.HarmonicFill, without an inpainting net")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
     args = ap.parse_args(argv)
@@ -84,7 +89,7 @@ def main(argv=None):
         nets.append(net.to(dev).eval())
     eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
-                          seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring)
+                          seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -109,7 +114,11 @@ def main(argv=None):
             for _, _, y0, x0, y1, x1 in eraser.last_regions["table"].tolist():
                 draw.rectangle([x0, y0, x1 - 1, y1 - 1], outline=(255, 0, 0))
             boxed.save(os.path.join(out_folder, name + "_boxes.png"))
-            print("%s: %d text regions, %d kept" % (name, eraser.last_regions["found"], eraser.last_regions["kept"]))
+            if args.group is not None:
+                print("%s: %d text regions in %d blocks, %d kept" % (name, eraser.last_regions["components"], eraser.last_regions["found"],
+                                                                     eraser.last_regions["kept"]))
+            else:
+                print("%s: %d text regions, %d kept" % (name, eraser.last_regions["found"], eraser.last_regions["kept"]))
         st = eraser.last_stats
         print("%s: %d x %d, %d of %d tiles inpainted, text fraction %.4f" %
               (name, page.shape[0], page.shape[1], st["selected"], st["tiles"], float((mask > 0).mean())))

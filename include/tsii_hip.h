@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 13
+#define TSII_ABI_VERSION 14
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -789,6 +789,41 @@ int tsii_flat_regions(const uint8_t* page, uint8_t* text, const int* labels, int
  * out, ws; out == x. */
 size_t tsii_harmonic_fill_ws_bytes(int n, int h, int w);
 int tsii_harmonic_fill(const float* x, const float* mask, int n, int h, int w, int sweeps, float* out, void* ws, void* stream);
+
+/* ---- K15: text blocks (csrc/blocks.hip) -- the components of a label plane grouped by distance, on the device: what the reference's demo
+ * calls "the text" is a block of lettering (a speech bubble's lines), while a component of tsii_text_regions is a glyph or a piece of one.
+ * Single linkage at Chebyshev distance `gap`.  All integer: the same inputs give the same bits on every run.
+ * Inputs: text uint8 [h,w], REWRITTEN IN PLACE; labels int32 [h,w], read only, as tsii_text_regions leaves it (normally called with
+ * min_area = 0, so that every text pixel has a label); gap 1..64.  F = {p : labels[p] != 0}; a pixel with text != 0 and labels == 0 is
+ * background.  The COMPONENTS are the label classes of F.  Two components are LINKED iff some pixel p of one and some pixel q of the
+ * other have max(|py - qy|, |px - qx|) <= gap; a BLOCK is a class of the transitive closure of LINKED.  Its LABEL is the smallest label
+ * of its components, 1 + min(y*w + x) over its pixels, its AREA its pixel count, its BOX y0, x0 inclusive and y1, x1 exclusive over its
+ * pixels, its MEMBERS the number of its components.  A block is KEPT iff area >= min_area (min_area <= 1 keeps everything).
+ *   block_labels[p], int32 [h,w] (never the plane `labels` itself) = the label of p's block if that block is kept, else 0
+ *   text[p]                  = block_labels[p] != 0 ? 1 : 0
+ *   n_blocks, int32 [2]      = {blocks found, blocks kept}
+ *   table, int32 [max_regions, 6]: row r = {label, area, y0, x0, y1, x1} of the r-th kept block in ascending label order.  Only the first
+ *     min(kept, max_regions) rows are written, the rows behind them are not touched; n_blocks[1] is the true count.
+ *   members, int32 [max_regions]: members[r] = MEMBERS of the block of table row r; the same rows are written, the others are not touched.
+ *     max_regions == 0 with table == NULL and members == NULL is allowed.
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the number of KEPT
+ *     text pixels in each tile core (integer atomics: independent of block order).
+ * The outputs follow tsii_text_regions: tsii_region_hulls, tsii_flat_regions and a window planner run behind this call unchanged, on
+ * (block_labels, table, n_blocks), and then work per block ("the pixels whose label is table[r][0]").
+ * How: F, one bit per pixel, gets a square of `gap` cells a side around every pixel ((gap-1)/2 cells towards larger y and x, the rest the other way; clipped
+ * to the page): two such squares overlap or touch, corners included, iff their pixels are at most `gap` apart, so the 8-connected components
+ * of the dilated plane -- labelled by tsii_text_regions itself, inside this call -- are the blocks.
+ * No allocation, no host synchronisation, everything on the caller's stream; no grid-wide barrier and no waiting on another block.
+ * ws: tsii_text_blocks_ws_bytes(h, w, max_regions, gap) bytes (0: arguments refused), 8-BYTE aligned; it depends on the size arguments
+ * only, needs nothing cleared beforehand and holds nothing a later call depends on (about 33 bytes per pixel: the bit plane, the dilated
+ * plane, its labels and the labelling's own workspace, which holds the blocks' statistics once the labelling is over).
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1; h*w > 2^31 - 2; gap outside 1..64; max_regions < 0 (or > 0
+ * without table and members); a NULL among text, labels, block_labels, n_blocks, ws; block_labels == labels; a bad tile geometry while
+ * core_count != NULL.  Labels that tsii_text_regions did not write give wrong blocks, never an access outside the buffers. */
+size_t tsii_text_blocks_ws_bytes(int h, int w, int max_regions, int gap);
+int tsii_text_blocks(uint8_t* text, const int* labels, int h, int w, int gap, int min_area, int max_regions,
+                     int tile, int halo, int* core_count, int* block_labels, int* table, int* members,
+                     int* n_blocks, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

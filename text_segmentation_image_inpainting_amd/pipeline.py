@@ -17,6 +17,9 @@ host by ``plan_fill_windows`` from the region boxes that the page's one synchron
 With ``flat`` the text regions that sit on one flat colour -- lettering in a speech bubble -- are painted with that colour on the device
 (``csrc/flat.hip``; "K13: flat regions") and never reach the filler: the reference README's "use the generated mask to white out
 words", applied where nothing has to be inferred.
+
+With ``group`` the regions are first grouped into blocks of lettering on the device (``csrc/blocks.hip``; "K15: text blocks"): the area
+filter, the hulls, the flat stage and ``pack`` then judge, fill, paint and place whole blocks instead of single glyphs.
 """
 from contextlib import contextmanager
 from typing import NamedTuple
@@ -29,8 +32,8 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import (_flat_regions, _region_hulls, _text_regions, check_flat_args, check_region_args, unpack_flat, unpack_hull_area,
-                      unpack_regions)
+from .regions import (_flat_regions, _region_hulls, _text_blocks, _text_regions, check_block_args, check_flat_args, check_region_args,
+                      unpack_blocks, unpack_flat, unpack_hull_area, unpack_regions)
 
 
 class TileGrid(NamedTuple):
@@ -307,6 +310,16 @@ class TextEraser:
     ``ring_pixels``.  Regions without a ring and kept regions beyond ``max_regions`` are never flat.  Still one synchronisation.
     ``None`` (the default): none of this runs.
 
+    ``group=G`` (an integer 1..64; turns the regions path on as well): the connected regions are grouped into BLOCKS first -- two regions
+    are in one block when some pixel of one is within ``G`` pixels (Chebyshev distance) of some pixel of the other, directly or through
+    other regions: the lines of a speech bubble with a ``G`` of about the line spacing -- and everything behind works on blocks:
+    ``min_area`` drops the blocks of fewer pixels (a dakuten beside its kana stays, a speck on its own goes), ``hull`` fills one hull
+    per block (the gaps between glyphs and lines close), ``flat`` without ``hull`` judges the ring around the whole block, ``pack``
+    plans its windows on the block boxes.  ``last_labels`` is then the block-label plane, ``last_regions["table"]`` the block table
+    (``found`` / ``kept`` count blocks) with ``members`` (numpy int32, the regions in each row's block) and ``components`` (the regions
+    of the page); ``last_stats`` gains ``blocks``.  Behind ``hull`` the flat stage labels the filled plane as before, ungrouped: hulls
+    are solid.  Still one synchronisation.  ``None`` (the default): none of this runs.
+
     The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
     the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
     ``clean`` equals the page wherever ``mask`` is 0.
@@ -314,7 +327,7 @@ class TextEraser:
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
-                 max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3):
+                 max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -333,7 +346,10 @@ class TextEraser:
         if flat is not None or flat_ring != 3:
             check_flat_args(0 if flat is None else flat, flat_ring)
         self.flat, self.flat_ring = None if flat is None else int(flat), int(flat_ring)
-        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack or self.flat is not None
+        if group is not None:
+            check_block_args(group)
+        self.group = None if group is None else int(group)
+        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack or self.flat is not None or self.group is not None
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -345,8 +361,8 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels")
-        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat")
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks")
+        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components")
         self.last_labels = None                         # its int32 label plane, left on the device
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
@@ -375,10 +391,25 @@ class TextEraser:
         return logits
 
     def _regions(self, text, g):
-        """filter the text plane in place -> ONE device tensor [filtered core counts | found, kept | table]; the labels stay on the device"""
-        self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g,
-                                                 tail=self.max_regions if self.hull else (5 * self.max_regions if self.flat is not None else 0))
+        """filter the text plane in place -> ONE device tensor [filtered core counts | found, kept | table]; the labels stay on the device.
+        With ``group`` the blocks stage filters: every region is labelled and no table is made here."""
+        if self.group is not None:
+            self.last_labels, packed = _text_regions(text, self.connectivity, 0, 0, g)
+            return packed
+        self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=self._tail())
         return packed
+
+    def _tail(self):
+        """the words behind the table that the stage behind it writes"""
+        return self.max_regions if self.hull else (5 * self.max_regions if self.flat is not None else 0)
+
+    def _blocks(self, text, g, packed):
+        """group the labelled regions into blocks and filter those, in place -> (the blocks' [core counts | found, kept | table], in the
+        layout ``_regions`` gives the regions' own, and the tensor it is the front of: members and the component count ride behind it);
+        ``last_labels`` becomes the block-label plane"""
+        self.last_labels, packed, whole = _text_blocks(text, self.last_labels, packed[g.count:g.count + 2], self.group, self.min_area,
+                                                       self.max_regions, g, tail=self._tail())
+        return packed, whole
 
     def _hulls(self, text, g, packed):
         """fill the kept regions' hulls into the text plane in place; packed becomes [core counts of the filled plane | ... | hull_area]"""
@@ -456,17 +487,27 @@ class TextEraser:
             src, compose_mask, split = page_d, mask_u8, 0   # src: the page the filler and compose see
             if self.regions:
                 counts = self._regions(text, g)
+                if self.group is not None:
+                    counts, whole = blocks = self._blocks(text, g, counts)
                 if self.hull:
                     counts = self._hulls(text, g, counts)
                 if self.flat is not None:               # the flat stage writes the page's mask; compose's, of the reduced plane, is scratch
                     counts, split, src = self._flat(page_d, text, g, counts, mask_u8)
                     compose_mask = torch.empty_like(mask_u8)
+                if self.group is not None:              # members and the component count: the last words of the read-back
+                    ride = int(blocks[0].numel())
+                    counts = whole if counts is blocks[0] else torch.cat([counts, whole[ride:]])
             counts_h = all_h = counts.cpu().numpy()     # the one synchronisation before the download
             flat_pixels = 0
             if self.regions:
+                if self.group is not None:
+                    all_h, blocks_h = all_h[:-(self.max_regions + 1)], all_h[-(self.max_regions + 1):]
                 packed_h = all_h[:split] if split else all_h
                 counts_h, table, found, kept, truncated = unpack_regions(packed_h, g.count, self.max_regions)
                 self.last_regions = {"table": table, "found": found, "kept": kept, "truncated": truncated}
+                if self.group is not None:
+                    members, components = unpack_blocks(blocks_h, 0, self.max_regions, len(table))
+                    self.last_regions.update(members=members, components=components)
                 if self.hull:
                     self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
                 if self.flat is not None:
@@ -489,6 +530,8 @@ class TextEraser:
                 _compose_page_u8(src, text, out, slot, g, clean, compose_mask)
         self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0,
                            "text_pixels": int(counts_h.sum()) + flat_pixels}
+        if self.group is not None:
+            self.last_stats.update(blocks=self.last_regions["kept"])
         if self.flat is not None:
             self.last_stats.update(flat_regions=int(is_flat.sum()), flat_pixels=flat_pixels)
         if self.pack:

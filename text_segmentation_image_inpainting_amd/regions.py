@@ -11,6 +11,11 @@ filled into the plane (``tsii_region_hulls``, ``csrc/hull.hip``; "K12: region hu
 ``flat_fill_regions`` is the reference README's middle step, "use the generated mask to white out words", for text on one flat colour:
 a region whose surrounding ring of page pixels is uniform within a tolerance is painted with the ring's mean colour and leaves the
 plane (``tsii_flat_regions``, ``csrc/flat.hip``; "K13: flat regions"); what is left is the text an inpainting net has to see.
+
+``text_blocks`` groups the regions into blocks of lettering: two regions belong together when some pixel of one is within ``gap`` pixels
+(Chebyshev distance) of some pixel of the other, and so on through their neighbours (``tsii_text_blocks``, ``csrc/blocks.hip``; "K15:
+text blocks").  The block labels and the block table have the form of the regions' own, so the hulls, the flat stage and the window
+planner work per block behind it.
 """
 from typing import NamedTuple
 
@@ -53,6 +58,26 @@ class TextRegions(NamedTuple):
     truncated: bool
 
 
+class TextBlocks(NamedTuple):
+    """``mask``: uint8 ``[H, W]`` of 0 / 255, the text of the kept blocks.  ``labels``: int32 ``[H, W]``, 0 = background or a dropped
+    block, else ``1 + min(y * W + x)`` over the block's pixels.  ``table``: numpy int32 ``[n, 6]``, one row ``(label, area, y0, x0, y1,
+    x1)`` per kept block in raster order of the blocks' first pixels, ``n = min(kept, max_regions)``; ``members``: numpy int32 ``[n]``,
+    the connected regions in each.  ``found`` / ``kept``: blocks before / after the area filter (``kept > len(table)``: the table is
+    cut at ``max_regions``).  ``components``: the connected regions of the plane."""
+    mask: object
+    labels: object
+    table: np.ndarray
+    members: np.ndarray
+    found: int
+    kept: int
+    components: int
+
+
+def check_block_args(gap):
+    if isinstance(gap, bool) or int(gap) != gap or not 1 <= gap <= 64:
+        raise ValueError(f"group gap {gap} must be an integer 1..64")
+
+
 def check_region_args(connectivity, min_area, max_regions):
     if connectivity not in (4, 8):
         raise ValueError(f"connectivity {connectivity} must be 4 or 8")
@@ -87,6 +112,35 @@ def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
     call("tsii_text_regions", ptr(text), h, w, int(connectivity), int(min_area), int(max_regions), tile, halo,
          ptr(packed[:nt]) if nt else None, ptr(labels), ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), ptr(ws), _lib.stream())
     return labels, packed
+
+
+def _text_blocks(text, labels, counts, gap, min_area, max_regions, grid=None, tail=0):
+    """``tsii_text_blocks`` in place on the device plane ``text``, behind the ``_text_regions`` call (``min_area=0``, same ``grid``) that
+    left ``labels`` and the device pair ``counts`` = its {found, kept} -> (block_labels, packed, whole).  ``packed`` has the layout
+    ``_text_regions`` gives its own, ``[core counts | found, kept | table rows | tail words]``, of the BLOCKS: ``_region_hulls``,
+    ``_flat_regions`` and ``unpack_regions`` take it as it is.  It is the front of ``whole``, the ONE tensor a caller reads back:
+    ``[packed | members (max_regions) | the components found]``."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    n = int(max_regions)
+    assert text.dtype == torch.uint8 and text.is_contiguous() and labels.shape == text.shape and labels.dtype == torch.int32
+    nbytes = int(_lib.lib().tsii_text_blocks_ws_bytes(h, w, n, int(gap)))
+    if nbytes == 0:
+        raise ValueError(f"text plane of {h} x {w} pixels, gap {gap}: out of range")
+    nt = 0 if grid is None else grid.count
+    front = nt + 2 + 6 * n + int(tail)
+    block_labels = torch.empty((h, w), dtype=torch.int32, device=text.device)
+    whole = torch.zeros((front + n + 1,), dtype=torch.int32, device=text.device)
+    whole[front + n:].copy_(counts[:1])
+    ws = ops._ws(nbytes, text)
+    tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
+    call("tsii_text_blocks", ptr(text), ptr(labels), h, w, int(gap), int(min_area), n, tile, halo, ptr(whole[:nt]) if nt else None,
+         ptr(block_labels), ptr(whole[nt + 2:]), ptr(whole[front:]), ptr(whole[nt:nt + 2]), ptr(ws), _lib.stream())
+    return block_labels, whole[:front], whole
+
+
+def unpack_blocks(whole_h, front, max_regions, n):
+    """host copy of ``whole`` (``front``: the words of its ``packed`` part) -> (members of the ``n`` table rows in use, components)"""
+    return whole_h[front:front + n].copy(), int(whole_h[front + int(max_regions)])
 
 
 def _region_hulls(text, labels, packed, max_regions, grid=None):
@@ -202,6 +256,25 @@ def flat_fill_regions(page_u8, mask_u8, tol, ring=3, connectivity=8, min_area=0,
     is_flat, colour, ring_pixels = unpack_flat(packed_h, 0, n, len(table))
     return FlatFill(_like(painted, page_u8), _like(plane * 255, mask_u8), TextRegions(_like(labels, mask_u8), table, found, kept, truncated),
                     is_flat, colour, ring_pixels)
+
+
+def text_blocks(mask_u8, gap, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextBlocks:
+    """Blocks of lettering in a text plane.  ``mask_u8``: ``[H, W]`` uint8, numpy or torch, host or device; non-zero = text (the 255 masks
+    ``TextEraser`` returns work directly); it is not modified.  The connected regions (``connectivity`` 4 or 8) are grouped by single
+    linkage: two regions are in one block when some pixel of one is within ``gap`` (1..64) pixels of some pixel of the other in both
+    axes, directly or through other regions.  Blocks of fewer than ``min_area`` pixels are dropped -- a small mark beside a glyph stays,
+    a speck on its own goes.  ``mask`` and ``labels`` come back the same kind and on the same device as ``mask_u8``; one
+    synchronisation (the read-back of the counts, the table and the members).  A host plane is computed on ``device`` (default
+    ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_block_args(gap)
+    plane = _plane_on_device(mask_u8, device)
+    labels, counts = _text_regions(plane, connectivity, 0, 0)
+    block_labels, packed, whole = _text_blocks(plane, labels, counts, gap, min_area, max_regions)
+    whole_h = whole.cpu().numpy()
+    _, table, found, kept, _ = unpack_regions(whole_h, 0, max_regions)
+    members, components = unpack_blocks(whole_h, int(packed.numel()), max_regions, len(table))
+    return TextBlocks(_like(plane * 255, mask_u8), _like(block_labels, mask_u8), table, members, found, kept, components)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

@@ -34,6 +34,10 @@ disc of one colour, as lettering sits in a speech bubble; ``--flat T`` (turns th
 (tsii_flat_regions, behind the regions / hulls stages; behind the hulls with the second labelling it needs, which is timed with it) and
 sends the filler only what is left.  ``regions`` then reports ``flat_regions`` / ``flat_pixels`` and ``labelled`` (the components the
 stage worked on).  Compare with a run on the same ``--bubbles`` page without ``--flat`` in the same session.
+
+``--group G`` (turns the regions stage on) adds the ``blocks`` stage (tsii_text_blocks, right behind the regions stage, which then labels
+every region and leaves the filter to the blocks): its own pair of events.  ``regions`` then counts blocks in ``found`` / ``kept`` and
+reports ``components`` and ``largest_block`` (members).  Compare with the same line without ``--group`` in the same session.
 """
 import argparse
 import json
@@ -107,6 +111,7 @@ def main(argv=None):
     ap.add_argument("--bubbles", type=float, default=None, metavar="SHARE", help="a noisy page with this share of the blobs on discs of one colour")
     ap.add_argument("--flat", type=int, default=None, metavar="T", help="time the flat stage (tsii_flat_regions) with this tolerance")
     ap.add_argument("--flat-ring", type=int, default=3)
+    ap.add_argument("--group", type=int, default=None, metavar="G", help="time the blocks stage (tsii_text_blocks): regions within G pixels form a block")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
     args = ap.parse_args(argv)
@@ -136,13 +141,14 @@ def main(argv=None):
         field = F.interpolate(torch.from_numpy(field)[None, None], size=(hs, ws), mode="nearest")[0, 0].numpy()
     logits_fixed = tile_logits(field, gs, dev)
     with_flat = args.flat is not None
-    with_regions = args.min_area > 0 or args.hull or args.pack or with_flat
+    with_blocks = args.group is not None
+    with_regions = args.min_area > 0 or args.hull or args.pack or with_flat or with_blocks
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
-                          flat=args.flat, flat_ring=args.flat_ring)
+                          flat=args.flat, flat_ring=args.flat_ring, group=args.group)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -152,8 +158,10 @@ def main(argv=None):
     stages = ["upload", "page_tiles_norm", "segmenter", "tiles_text_mask", "counts_d2h", "page_tiles_fill", "filler", "compose_page_u8", "download"]
     if with_regions:
         stages.append("regions")                            # timed with its own pair of events, between the mask and the read-back
+    if with_blocks:
+        stages.append("blocks")                             # its own pair of events, right behind the regions stage
     if args.hull:
-        stages.append("hulls")                              # its own pair of events, right behind the regions stage
+        stages.append("hulls")                              # its own pair of events, right behind the regions (or blocks) stage
     if with_flat:
         stages.append("flat")                               # its own pair of events, behind the regions / hulls stages
     if with_seg:
@@ -161,7 +169,7 @@ def main(argv=None):
 
     def one_page():
         marks = [ev() for _ in range(11)]
-        reg0, reg1, hul1, res1, up0, up1, fl0, fl1 = ev(), ev(), ev(), ev(), ev(), ev(), ev(), ev()
+        reg0, reg1, hul1, res1, up0, up1, fl0, fl1, blk1 = ev(), ev(), ev(), ev(), ev(), ev(), ev(), ev(), ev()
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
@@ -187,6 +195,9 @@ def main(argv=None):
                 reg0.record()
                 counts = eraser._regions(text, g)           # tsii_text_regions; the labels stay in eraser.last_labels
                 reg1.record()
+                if with_blocks:
+                    counts, whole = blocks = eraser._blocks(text, g, counts)     # tsii_text_blocks; last_labels becomes the block labels
+                    blk1.record()
                 if args.hull:
                     counts = eraser._hulls(text, g, counts)
                     hul1.record()
@@ -196,20 +207,28 @@ def main(argv=None):
                 fl0.record()
                 counts, split, src = eraser._flat(page_d, text, g, counts, page_mask)
                 fl1.record()
+            if with_blocks:                                 # members and the component count ride at the end, as in the eraser
+                counts = whole if counts is blocks[0] else torch.cat([counts, whole[int(blocks[0].numel()):]])
             marks[4].record()
-            counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table + flat rows)
+            counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table + flat rows + members)
             marks[5].record()
             d2h_words = int(counts_h.size)
             region_info = None
             if with_regions:
                 packed_h = counts_h
+                if with_blocks:
+                    packed_h, blocks_h = counts_h[:-(args.max_regions + 1)], counts_h[-(args.max_regions + 1):]
                 counts_h, table, found, kept, truncated = RG.unpack_regions(packed_h, g.count, args.max_regions)
                 region_info = {"found": found, "kept": kept, "truncated": truncated}
+                if with_blocks:
+                    members, components = RG.unpack_blocks(blocks_h, 0, args.max_regions, len(table))
+                    region_info.update(components=components, largest_block=int(members.max()) if len(members) else 0)
                 if args.hull:
                     region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h[:split] if split else packed_h, g.count, args.max_regions,
                                                                          len(table)).sum(dtype=np.int64))
                 if with_flat:                               # everything behind works on the flat stage's own components and counts
                     own = packed_h[split:]
+                    packed_h = packed_h[:split] if split else packed_h
                     counts_h, ftable, _, _, truncated = RG.unpack_regions(own, g.count, args.max_regions)
                     is_flat = RG.unpack_flat(own, g.count, args.max_regions, len(ftable))[0]
                     region_info.update(labelled=len(ftable), flat_regions=int(is_flat.sum()),
@@ -255,8 +274,10 @@ def main(argv=None):
         if with_regions:
             t[3] = marks[3].elapsed_time(reg0)
             t.append(reg0.elapsed_time(reg1))
+        if with_blocks:
+            t.append(reg1.elapsed_time(blk1))
         if args.hull:
-            t.append(reg1.elapsed_time(hul1))
+            t.append((blk1 if with_blocks else reg1).elapsed_time(hul1))
         if with_flat:
             t.append(fl0.elapsed_time(fl1))
         if with_seg:
@@ -289,6 +310,8 @@ def main(argv=None):
         bytes_.update(resize=3 * npx + 3 * nsp, plane_up=nsp + npx)      # DESIGN.md, "working resolution"
     if with_regions:
         bytes_["regions"] = 18 * npx        # local 1 + 4, measure 4, filter 4 + 4 + 1 ("text regions"); seams and statistics on top
+    if with_blocks:                         # DESIGN.md, "text blocks": pack 4, dilate 1, the labelling of the dilated plane 18, min 4 (+ runs),
+        bytes_["blocks"] = 48 * npx         # name 4 + 4 + 4, measure 4, filter 4 + 4 + 1
     if args.hull:
         bytes_["hulls"] = 5 * npx + n_text  # extents 4 (labels), finish 1, the fill's stores at most once per final text pixel ("region hulls")
     if with_flat:                           # DESIGN.md, "flat regions": ring 1 (text) + apron, apply 3 + 1 in, 3 + 1 + 1 out, labels on the text
@@ -411,7 +434,7 @@ def main(argv=None):
         # the stages that copy to the host before the download: still one, whatever it carries
         "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
         "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
-        "bubbles": args.bubbles, "flat": args.flat, "flat_ring": args.flat_ring if with_flat else None,
+        "bubbles": args.bubbles, "flat": args.flat, "flat_ring": args.flat_ring if with_flat else None, "group": args.group,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
