@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 14
+#define TSII_ABI_VERSION 15
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -824,6 +824,57 @@ size_t tsii_text_blocks_ws_bytes(int h, int w, int max_regions, int gap);
 int tsii_text_blocks(uint8_t* text, const int* labels, int h, int w, int gap, int min_area, int max_regions,
                      int tile, int halo, int* core_count, int* block_labels, int* table, int* members,
                      int* n_blocks, void* ws, void* stream);
+
+/* ---- K16: smooth regions (csrc/smooth.hip) -- the middle route between K13 and an inpainting net: a text region whose surrounding RING of
+ * page pixels is LOCALLY SMOOTH (a gradient, a soft shadow, a sky: no hard edge crosses it) is filled with the harmonic continuation of
+ * its surroundings at page level and leaves the text plane; only what is left goes to a net.  Two entry points on either side of
+ * tsii_harmonic_fill (K14), which the caller runs unchanged between them:
+ *     tsii_smooth_regions_classify(..., smooth, x, valid, ws, stream);
+ *     tsii_harmonic_fill(x, valid, 1, h, w, sweeps, filled, ws', stream);
+ *     tsii_smooth_regions_apply(..., smooth, filled, ..., painted, mask, stream);
+ * The decision is all integer: exact, the same bits on every run.
+ * Inputs as K13 takes them: page uint8 [h,w,3]; text uint8 [h,w] (non-zero = text; classify reads it, apply REWRITES IT IN PLACE); labels
+ * int32 [h,w], table int32 [max_regions,6] and n_regions int32 [2] ON THE DEVICE exactly as tsii_text_regions or tsii_text_blocks left
+ * them; ring 1..8; tol 0..255.  Only the label column of the table is read.  R = min(n_regions[1], max_regions); for r < R:
+ *   C_r      the pixels whose label is table[r][0] AND whose text byte is non-zero on entry.  A region tsii_flat_regions has painted (its
+ *            text bytes cleared, its labels left) has an empty C_r: the stage composes behind K13 with the same labels and table
+ *   Ring_r   K13's ring: the page pixels q with text[q] == 0 on entry for which some p in C_r has max(|qy - py|, |qx - px|) <= ring.  A
+ *            pixel may lie in several rings; text pixels lie in none; the page edge clips the ring.  n_r = |Ring_r|
+ *   d_c(q)   for a pixel q with text[q] == 0: the largest |page[q][c] - page[q'][c]| over the 4-neighbours q' of q that are on the page
+ *            and have text[q'] == 0; 0 without one.  It depends on the pixel only, not on the region
+ *   step_r[c] = max of d_c(q) over Ring_r (0 where n_r == 0)
+ *   smooth_r iff n_r >= 1 and step_r[c] <= tol for all three channels.  A hard edge that crosses the region crosses its ring; a gradient
+ *            of slope <= tol per pixel does not trip it; a ring that K13 calls flat at `tol` is smooth at `tol`
+ * Outputs of classify:
+ *   smooth, int32 [max_regions,5]: row r < R = {smooth_r, step_r[0], step_r[1], step_r[2], n_r}; the rows behind R are not touched
+ *   x, fp32 [h,w,3] = (float)page byte / 255.0f (the IEEE quotient); valid, fp32 [h,w] = 1.0 where text == 0, else 0.0: the operands of
+ *            tsii_harmonic_fill for n = 1.  The solver's holes are ALL the text on entry: the ink of a neighbouring region that is not
+ *            smooth is never valid context
+ *   page, text, labels, table and n_regions are read only.
+ * apply (smooth: as classify left it; filled fp32 [h,w,3]: the solver's output, read on the pixels of C_r of smooth rows ONLY -- it may hold
+ * anything elsewhere):
+ *   painted, uint8 [h,w,3] (not the page itself): floor(clamp(filled, 0, 1) * 255 + 0.5) -- the product and the sum each rounded to fp32 --
+ *            on C_r where smooth_r holds, the page byte everywhere else
+ *   text[p]  = 0 on the smooth regions, 1 where it was non-zero otherwise, else 0.  Regions beyond the table are never smooth and stay text
+ *   mask, uint8 [h,w] or NULL: 255 where text was non-zero ON ENTRY, else 0
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the text pixels of
+ *            the FINAL plane in each tile core (integer atomics: independent of block order)
+ *   labels, table, n_regions, smooth and filled are read only.
+ * No allocation, no host synchronisation, everything on the caller's stream; no grid-wide barrier and no waiting on another block.
+ * ws (classify): tsii_smooth_regions_ws_bytes(h, w, max_regions) bytes (0: geometry refused), 4-byte aligned; it depends on (h, w,
+ * max_regions) only, needs nothing cleared beforehand and holds nothing a later call depends on.  x and valid take 16-byte stores where
+ * they (and page and text, for 4-byte loads) are aligned for them, scalar ones otherwise.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1; h*w*3 > 2^31; max_regions < 1; ring outside 1..8 or tol outside
+ * 0..255 (classify); a NULL among page, text, labels, table, n_regions, smooth and x, valid, ws (classify) or filled, painted (apply);
+ * painted == page; a bad tile geometry while core_count != NULL.  The count read from n_regions is clamped to max_regions and every table
+ * row is found by a search below it: a table that does not belong to the labels gives wrong bytes, never an access outside the buffers. */
+size_t tsii_smooth_regions_ws_bytes(int h, int w, int max_regions);
+int tsii_smooth_regions_classify(const uint8_t* page, const uint8_t* text, const int* labels, int h, int w, const int* table,
+                                 const int* n_regions, int max_regions, int ring, int tol, int* smooth, float* x, float* valid, void* ws,
+                                 void* stream);
+int tsii_smooth_regions_apply(const uint8_t* page, uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
+                              int max_regions, const int* smooth, const float* filled, int tile, int halo, int* core_count,
+                              uint8_t* painted, uint8_t* mask, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 14          # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 15          # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -175,6 +175,10 @@ SIGNATURES = {
     # K15 text blocks (csrc/blocks.hip): the text plane in place behind tsii_text_regions, int32 block labels / table / members; ws 8-byte aligned
     "tsii_text_blocks_ws_bytes": (_z, [_i, _i, _i, _i]),
     "tsii_text_blocks": (_i, [_p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    # K16 smooth regions (csrc/smooth.hip): classify and apply on either side of tsii_harmonic_fill; int32 smooth rows, fp32 x / valid / filled
+    "tsii_smooth_regions_ws_bytes": (_z, [_i, _i, _i]),
+    "tsii_smooth_regions_classify": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "tsii_smooth_regions_apply": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _p, _p, _i, _i, _p, _p, _p, _p]),
 }
 
 _LIB = None

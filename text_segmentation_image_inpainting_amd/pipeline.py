@@ -18,6 +18,10 @@ With ``flat`` the text regions that sit on one flat colour -- lettering in a spe
 (``csrc/flat.hip``; "K13: flat regions") and never reach the filler: the reference README's "use the generated mask to white out
 words", applied where nothing has to be inferred.
 
+With ``smooth`` the regions whose surroundings are locally smooth -- lettering on a gradient, a soft shadow, a sky -- are filled with the
+harmonic continuation of those surroundings at page level (``csrc/smooth.hip``; "K16: smooth regions", around the solver of
+``csrc/harmonic.hip``) and never reach the filler either: flat, then smooth, then the net, decided per region on the device.
+
 With ``group`` the regions are first grouped into blocks of lettering on the device (``csrc/blocks.hip``; "K15: text blocks"): the area
 filter, the hulls, the flat stage and ``pack`` then judge, fill, paint and place whole blocks instead of single glyphs.
 """
@@ -32,8 +36,8 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import (_flat_regions, _region_hulls, _text_blocks, _text_regions, check_block_args, check_flat_args, check_region_args,
-                      unpack_blocks, unpack_flat, unpack_hull_area, unpack_regions)
+from .regions import (_flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, check_block_args, check_flat_args,
+                      check_region_args, check_smooth_args, unpack_blocks, unpack_flat, unpack_hull_area, unpack_regions, unpack_smooth)
 
 
 class TileGrid(NamedTuple):
@@ -310,6 +314,18 @@ class TextEraser:
     ``ring_pixels``.  Regions without a ring and kept regions beyond ``max_regions`` are never flat.  Still one synchronisation.
     ``None`` (the default): none of this runs.
 
+    ``smooth=T`` (an integer 0..255; turns the regions path on as well): the route between ``flat`` and the filler.  A text region is SMOOTH
+    when no pixel of its ring -- ``smooth_ring`` (1..8) wide, as for ``flat`` -- differs from a neighbouring pixel that is not text by more
+    than ``T`` grey levels in any channel: a gradient, a soft shadow or a sky passes, a hard edge or screentone across the region does
+    not.  Such a region is filled with the harmonic continuation of the pixels around the page's text (``harmonic_fill`` on the whole
+    page with ``smooth_sweeps`` sweeps: the same bytes), right behind the flat stage and on the page that stage painted; it selects no
+    tile, is no hole for the filler -- which sees the filled pixels as valid context -- and is not among the boxes ``pack`` places its
+    windows on; a page whose text is all flat or smooth never calls the filler.  The stage works on the labels and the table the flat
+    stage works on (the second labelling behind ``hull`` is done once for both).  The returned mask still holds every region.
+    ``last_stats`` gains ``smooth_regions`` and ``smooth_pixels``, ``last_regions`` gains ``smooth``: a dict of ``table``, ``is_smooth``,
+    ``step`` (uint8 ``[n, 3]``: the largest step between neighbours in each ring) and ``ring_pixels``.  Still one synchronisation.
+    ``None`` (the default): none of this runs.
+
     ``group=G`` (an integer 1..64; turns the regions path on as well): the connected regions are grouped into BLOCKS first -- two regions
     are in one block when some pixel of one is within ``G`` pixels (Chebyshev distance) of some pixel of the other, directly or through
     other regions: the lines of a speech bubble with a ``G`` of about the line spacing -- and everything behind works on blocks:
@@ -327,7 +343,8 @@ class TextEraser:
 
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
-                 max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None):
+                 max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
+                 smooth_ring=3, smooth_sweeps=8):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -349,7 +366,11 @@ class TextEraser:
         if group is not None:
             check_block_args(group)
         self.group = None if group is None else int(group)
-        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack or self.flat is not None or self.group is not None
+        if smooth is not None or smooth_ring != 3 or smooth_sweeps != 8:
+            check_smooth_args(0 if smooth is None else smooth, smooth_ring, smooth_sweeps)
+        self.smooth, self.smooth_ring, self.smooth_sweeps = None if smooth is None else int(smooth), int(smooth_ring), int(smooth_sweeps)
+        self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.flat is not None or self.group is not None
+                        or self.smooth is not None)
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -361,8 +382,8 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks")
-        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components")
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks"; + "smooth_regions", "smooth_pixels")
+        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components"; + "smooth")
         self.last_labels = None                         # its int32 label plane, left on the device
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
@@ -401,7 +422,11 @@ class TextEraser:
 
     def _tail(self):
         """the words behind the table that the stage behind it writes"""
-        return self.max_regions if self.hull else (5 * self.max_regions if self.flat is not None else 0)
+        return self.max_regions if self.hull else self._route_tail()
+
+    def _route_tail(self):
+        """the words behind the table of the labelling the flat and smooth stages work on: 5 per row and stage, flat rows first"""
+        return 5 * self.max_regions * ((self.flat is not None) + (self.smooth is not None))
 
     def _blocks(self, text, g, packed):
         """group the labelled regions into blocks and filter those, in place -> (the blocks' [core counts | found, kept | table], in the
@@ -416,19 +441,35 @@ class TextEraser:
         _region_hulls(text, self.last_labels, packed, self.max_regions, g)
         return packed
 
-    def _flat(self, page_d, text, g, packed, mask_u8):
-        """paint the flat regions and take them out of the text plane in place -> (ONE device tensor for the read-back, the number of
-        its leading words that belong to the stages before, the painted page); ``mask_u8`` gets the mask of the whole plane.  Behind the
-        hulls the filled plane is labelled once more and that call's tensor ``[core counts | found, kept | table | flat rows]`` rides
-        behind ``packed``; otherwise the flat rows are the tail of ``packed`` itself.  The core counts of the reduced plane are at the
-        front of the part behind ``split``."""
-        labels, own, split = self.last_labels, packed, 0
+    def _route_labels(self, text, g, packed):
+        """what the flat and smooth stages work on -> (labels, ONE device tensor ``[core counts | found, kept | table | flat rows | smooth
+        rows]``, the number of words of ``packed`` that ride in front of it in the read-back).  Behind the hulls the filled plane is
+        labelled once more, for both stages (hull pixels carry no label), and that call's tensor rides behind ``packed``; otherwise the
+        rows are the tail of ``packed`` itself and nothing rides in front."""
         if self.hull:
-            labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=5 * self.max_regions)
-            split = int(packed.numel())
+            labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=self._route_tail())
+            return labels, own, int(packed.numel())
+        return self.last_labels, packed, 0
+
+    def _flat(self, page_d, text, g, route, mask_u8):
+        """paint the flat regions and take them out of the text plane in place -> the painted page; ``mask_u8`` gets the mask of the whole
+        plane.  ``route``: ``_route_labels``' triple; the core counts of the reduced plane are at the front of its tensor."""
+        labels, own, _ = route
         painted = torch.empty_like(page_d)
         _flat_regions(page_d, text, labels, own, self.max_regions, self.flat_ring, self.flat, painted, mask_u8, g)
-        return (torch.cat([packed, own]) if split else packed), split, painted
+        return painted
+
+    def _smooth(self, src, text, g, route, mask_u8):
+        """fill the smooth regions harmonically and take them out of the text plane in place -> the filled page (a new buffer; ``src``:
+        the page, or the flat stage's).  ``mask_u8``: the plane that gets the mask of the whole plane on entry, None where the flat stage
+        wrote the page's already.  The smooth rows ride behind the flat rows of ``route``'s tensor, the core counts at its front are
+        rewritten for the reduced plane."""
+        labels, own, _ = route
+        n, at = self.max_regions, g.count + 2 + 6 * self.max_regions + (5 * self.max_regions if self.flat is not None else 0)
+        painted = torch.empty_like(src)
+        _smooth_regions(src, text, labels, own[g.count + 2:], own[g.count:g.count + 2], own[at:at + 5 * n], n, self.smooth_ring, self.smooth,
+                        self.smooth_sweeps, painted, mask_u8, g, own[:g.count])
+        return painted
 
     def _run_filler(self, img, mplane, g):
         """fp32 NHWC tiles and their mask planes through the filler, ``tile_batch`` at a time -> its outputs, fp32 NHWC"""
@@ -491,14 +532,20 @@ class TextEraser:
                     counts, whole = blocks = self._blocks(text, g, counts)
                 if self.hull:
                     counts = self._hulls(text, g, counts)
-                if self.flat is not None:               # the flat stage writes the page's mask; compose's, of the reduced plane, is scratch
-                    counts, split, src = self._flat(page_d, text, g, counts, mask_u8)
+                if self.flat is not None or self.smooth is not None:
+                    route = self._route_labels(text, g, counts)
+                    if self.flat is not None:           # the first of the two stages writes the page's mask; compose's, of the reduced plane, is scratch
+                        src = self._flat(page_d, text, g, route, mask_u8)
+                    if self.smooth is not None:
+                        src = self._smooth(src, text, g, route, None if self.flat is not None else mask_u8)
                     compose_mask = torch.empty_like(mask_u8)
+                    split = route[2]
+                    counts = torch.cat([counts, route[1]]) if split else route[1]
                 if self.group is not None:              # members and the component count: the last words of the read-back
                     ride = int(blocks[0].numel())
                     counts = whole if counts is blocks[0] else torch.cat([counts, whole[ride:]])
             counts_h = all_h = counts.cpu().numpy()     # the one synchronisation before the download
-            flat_pixels = 0
+            flat_pixels = smooth_pixels = 0
             if self.regions:
                 if self.group is not None:
                     all_h, blocks_h = all_h[:-(self.max_regions + 1)], all_h[-(self.max_regions + 1):]
@@ -510,13 +557,21 @@ class TextEraser:
                     self.last_regions.update(members=members, components=components)
                 if self.hull:
                     self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
-                if self.flat is not None:
+                if self.flat is not None or self.smooth is not None:
                     packed_h = all_h[split:]            # behind the hulls: the filled plane's own components; all that follows works on them
                     counts_h, ftable, _, _, ftruncated = unpack_regions(packed_h, g.count, self.max_regions)
-                    is_flat, colour, ring_pixels = unpack_flat(packed_h, g.count, self.max_regions, len(ftable))
-                    self.last_regions["flat"] = {"table": ftable, "is_flat": is_flat, "colour": colour, "ring_pixels": ring_pixels}
-                    flat_pixels = int(ftable[is_flat, 1].sum(dtype=np.int64))
-                    table, truncated = ftable[~is_flat], ftruncated     # what pack plans its windows on
+                    gone, at = np.zeros(len(ftable), bool), g.count + 2 + 6 * self.max_regions
+                    if self.flat is not None:
+                        is_flat, colour, ring_pixels = unpack_flat(packed_h, g.count, self.max_regions, len(ftable))
+                        self.last_regions["flat"] = {"table": ftable, "is_flat": is_flat, "colour": colour, "ring_pixels": ring_pixels}
+                        flat_pixels = int(ftable[is_flat, 1].sum(dtype=np.int64))
+                        gone, at = gone | is_flat, at + 5 * self.max_regions
+                    if self.smooth is not None:         # a flat region has no text left: its smooth row is empty
+                        is_smooth, step, ring_pixels = unpack_smooth(packed_h[at:], len(ftable))
+                        self.last_regions["smooth"] = {"table": ftable, "is_smooth": is_smooth, "step": step, "ring_pixels": ring_pixels}
+                        smooth_pixels = int(ftable[is_smooth, 1].sum(dtype=np.int64))
+                        gone = gone | is_smooth
+                    table, truncated = ftable[~gone], ftruncated        # what pack plans its windows on
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
             windows = self._plan(table, truncated, g, len(selected)) if (self.pack and any_text) else None
@@ -529,11 +584,13 @@ class TextEraser:
             else:
                 _compose_page_u8(src, text, out, slot, g, clean, compose_mask)
         self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0,
-                           "text_pixels": int(counts_h.sum()) + flat_pixels}
+                           "text_pixels": int(counts_h.sum()) + flat_pixels + smooth_pixels}
         if self.group is not None:
             self.last_stats.update(blocks=self.last_regions["kept"])
         if self.flat is not None:
             self.last_stats.update(flat_regions=int(is_flat.sum()), flat_pixels=flat_pixels)
+        if self.smooth is not None:
+            self.last_stats.update(smooth_regions=int(is_smooth.sum()), smooth_pixels=smooth_pixels)
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)

@@ -12,6 +12,11 @@ filled into the plane (``tsii_region_hulls``, ``csrc/hull.hip``; "K12: region hu
 a region whose surrounding ring of page pixels is uniform within a tolerance is painted with the ring's mean colour and leaves the
 plane (``tsii_flat_regions``, ``csrc/flat.hip``; "K13: flat regions"); what is left is the text an inpainting net has to see.
 
+``smooth_fill_regions`` is the route between that and a net, for text on a smooth background (a gradient, a soft shadow, a sky): a region
+whose ring shows no step of more than a tolerance between neighbouring pixels is filled with the harmonic continuation of its
+surroundings at page level (``tsii_smooth_regions_classify`` / ``tsii_smooth_regions_apply``, ``csrc/smooth.hip``; "K16: smooth regions",
+around the ``tsii_harmonic_fill`` of ``fill.py``) and leaves the plane.
+
 ``text_blocks`` groups the regions into blocks of lettering: two regions belong together when some pixel of one is within ``gap`` pixels
 (Chebyshev distance) of some pixel of the other, and so on through their neighbours (``tsii_text_blocks``, ``csrc/blocks.hip``; "K15:
 text blocks").  The block labels and the block table have the form of the regions' own, so the hulls, the flat stage and the window
@@ -24,6 +29,7 @@ import torch
 
 from . import _lib, ops
 from ._lib import call, ptr
+from .fill import _harmonic_fill, check_sweeps
 
 
 class RegionHulls(NamedTuple):
@@ -43,6 +49,19 @@ class FlatFill(NamedTuple):
     regions: "TextRegions"
     is_flat: np.ndarray
     colour: np.ndarray
+    ring_pixels: np.ndarray
+
+
+class SmoothFill(NamedTuple):
+    """``painted``: uint8 ``[H, W, 3]``, the page with every smooth region filled harmonically.  ``text``: uint8 ``[H, W]`` of 0 / 255,
+    the text that is left for a net.  ``table``: numpy int32 ``[n, 6]``, the region table (``TextRegions.table``).  Per table row:
+    ``is_smooth`` (numpy bool ``[n]``), ``step`` (uint8 ``[n, 3]``, the largest difference between 4-neighbours in the ring, per channel;
+    0 without a ring) and ``ring_pixels`` (int32 ``[n]``)."""
+    painted: object
+    text: object
+    table: np.ndarray
+    is_smooth: np.ndarray
+    step: np.ndarray
     ring_pixels: np.ndarray
 
 
@@ -92,6 +111,17 @@ def check_flat_args(tol, ring):
         raise ValueError(f"flat tolerance {tol} must be an integer 0..255")
     if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 8:
         raise ValueError(f"flat ring {ring} must be an integer 1..8")
+
+
+def check_smooth_args(tol, ring, sweeps):
+    if isinstance(tol, bool) or int(tol) != tol or not 0 <= tol <= 255:
+        raise ValueError(f"smooth tolerance {tol} must be an integer 0..255")
+    if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 8:
+        raise ValueError(f"smooth ring {ring} must be an integer 1..8")
+    try:
+        check_sweeps(sweeps)
+    except ValueError as e:
+        raise ValueError(f"smooth {e}") from None
 
 
 def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
@@ -168,7 +198,7 @@ def _flat_regions(page, text, labels, packed, max_regions, ring, tol, painted, m
     h, w = int(text.shape[0]), int(text.shape[1])
     nt = 0 if grid is None else grid.count
     n = int(max_regions)
-    assert packed.numel() == nt + 2 + 11 * n and packed.dtype == torch.int32 and packed.device == text.device
+    assert packed.numel() >= nt + 2 + 11 * n and packed.dtype == torch.int32 and packed.device == text.device
     assert page.shape == (h, w, 3) and painted.shape == (h, w, 3) and all(t.dtype == torch.uint8 and t.is_contiguous() for t in (page, painted))
     assert mask is None or (mask.shape == (h, w) and mask.dtype == torch.uint8 and mask.is_contiguous())
     nbytes = int(_lib.lib().tsii_flat_regions_ws_bytes(h, w, n))
@@ -178,6 +208,37 @@ def _flat_regions(page, text, labels, packed, max_regions, ring, tol, painted, m
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
     call("tsii_flat_regions", ptr(page), ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, int(ring), int(tol),
          tile, halo, ptr(packed[:nt]) if nt else None, ptr(painted), ptr(mask), ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+
+
+def _smooth_regions(page, text, labels, table, n_regions, rows, max_regions, ring, tol, sweeps, painted, mask=None, grid=None, core_count=None):
+    """``tsii_smooth_regions_classify``, ``tsii_harmonic_fill`` on the whole page and ``tsii_smooth_regions_apply`` on the current stream,
+    in place on the device plane ``text``: ``labels``, ``table`` (the device words of the table) and ``n_regions`` (the device pair) as the
+    labelling -- or the flat stage behind it -- left them; ``rows``: ``5 * max_regions`` device words for the smooth rows; ``core_count``
+    (with ``grid``) is rewritten for the reduced plane.  ``painted`` (and ``mask``, the 0 / 255 plane of the text on entry) are written."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    n = int(max_regions)
+    assert rows.numel() == 5 * n and rows.dtype == torch.int32 and rows.device == text.device and rows.is_contiguous()
+    assert page.shape == (h, w, 3) and painted.shape == (h, w, 3) and all(t.dtype == torch.uint8 and t.is_contiguous() for t in (page, painted, text))
+    assert mask is None or (mask.shape == (h, w) and mask.dtype == torch.uint8 and mask.is_contiguous())
+    nbytes = int(_lib.lib().tsii_smooth_regions_ws_bytes(h, w, n))
+    if nbytes == 0:
+        raise ValueError(f"text plane of {h} x {w} pixels is out of range")
+    x = torch.empty((1, h, w, 3), dtype=torch.float32, device=text.device)
+    valid = torch.empty((1, h, w), dtype=torch.float32, device=text.device)
+    ws = ops._ws(nbytes, text)
+    call("tsii_smooth_regions_classify", ptr(page), ptr(text), ptr(labels), h, w, ptr(table), ptr(n_regions), n, int(ring), int(tol), ptr(rows),
+         ptr(x), ptr(valid), ptr(ws), _lib.stream())
+    filled = _harmonic_fill(x, valid, int(sweeps))
+    tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
+    call("tsii_smooth_regions_apply", ptr(page), ptr(text), ptr(labels), h, w, ptr(table), ptr(n_regions), n, ptr(rows), ptr(filled), tile, halo,
+         ptr(core_count) if grid is not None else None, ptr(painted), ptr(mask), _lib.stream())
+
+
+def unpack_smooth(rows_h, n):
+    """host copy of the smooth rows -> (is_smooth bool ``[n]``, step uint8 ``[n, 3]``, ring_pixels int32 ``[n]``) of the ``n`` table rows
+    in use"""
+    rows = rows_h[:5 * n].reshape(n, 5)
+    return rows[:, 0] != 0, rows[:, 1:4].astype(np.uint8), rows[:, 4].copy()
 
 
 def unpack_flat(packed_h, nt, max_regions, n):
@@ -256,6 +317,33 @@ def flat_fill_regions(page_u8, mask_u8, tol, ring=3, connectivity=8, min_area=0,
     is_flat, colour, ring_pixels = unpack_flat(packed_h, 0, n, len(table))
     return FlatFill(_like(painted, page_u8), _like(plane * 255, mask_u8), TextRegions(_like(labels, mask_u8), table, found, kept, truncated),
                     is_flat, colour, ring_pixels)
+
+
+def smooth_fill_regions(page_u8, mask_u8, tol, ring=3, sweeps=8, connectivity=8, min_area=0, max_regions=4096, device=None) -> SmoothFill:
+    """Fill the text that sits on a smooth background.  ``page_u8``: ``[H, W, 3]`` uint8; ``mask_u8``: ``[H, W]`` uint8, non-zero = text (the
+    255 masks ``TextEraser`` returns work directly); numpy or torch, host or device, neither is modified.  Regions below ``min_area`` are
+    dropped first, as in ``text_regions``.  A kept region is SMOOTH when no page pixel within ``ring`` (1..8, Chebyshev distance) of it
+    that is not text itself differs from a 4-neighbour that is not text by more than ``tol`` (0..255) grey levels in any channel: a
+    gradient passes, a hard edge across the region does not.  It is filled with the harmonic continuation of the pixels around the
+    text (``harmonic_fill`` on the whole page and the whole mask, ``sweeps`` 0..16: the same bytes) and leaves ``text``.  Regions without
+    a ring, and kept regions beyond ``max_regions``, are never smooth.  ``painted`` comes back the same kind and on the same device as
+    ``page_u8``, ``text`` as ``mask_u8``; one synchronisation (the read-back of the counts, the table and the smooth rows).  Host
+    arguments are computed on ``device`` (default ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_smooth_args(tol, ring, sweeps)
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
+        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
+    plane = _plane_on_device(mask_u8, device)
+    page = p.to(plane.device).contiguous()
+    n = int(max_regions)
+    labels, packed = _text_regions(plane, connectivity, min_area, n, tail=5 * n)
+    painted = torch.empty_like(page)
+    _smooth_regions(page, plane, labels, packed[2:], packed[:2], packed[2 + 6 * n:], n, ring, tol, sweeps, painted)
+    packed_h = packed.cpu().numpy()
+    _, table, _, _, _ = unpack_regions(packed_h, 0, n)
+    is_smooth, step, ring_pixels = unpack_smooth(packed_h[2 + 6 * n:], len(table))
+    return SmoothFill(_like(painted, page_u8), _like(plane * 255, mask_u8), table, is_smooth, step, ring_pixels)
 
 
 def text_blocks(mask_u8, gap, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextBlocks:

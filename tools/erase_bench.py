@@ -3,7 +3,7 @@
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
                                 [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
-                                [--bubbles SHARE] [--flat T [--flat-ring N]]
+                                [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -34,6 +34,11 @@ disc of one colour, as lettering sits in a speech bubble; ``--flat T`` (turns th
 (tsii_flat_regions, behind the regions / hulls stages; behind the hulls with the second labelling it needs, which is timed with it) and
 sends the filler only what is left.  ``regions`` then reports ``flat_regions`` / ``flat_pixels`` and ``labelled`` (the components the
 stage worked on).  Compare with a run on the same ``--bubbles`` page without ``--flat`` in the same session.
+
+``--ramps SHARE`` is ``--bubbles`` with a linear colour ramp on every ellipse instead of one colour; ``--smooth T`` (turns the regions
+stage on) adds the ``smooth`` stage (tsii_smooth_regions_classify, tsii_harmonic_fill on the whole page, tsii_smooth_regions_apply, behind
+the flat stage; with its own pair of events, and, with the net as the filler, split into its three calls by events around each:
+``smooth_split_ms``).  Compare with a run on the same ``--ramps`` page without ``--smooth`` in the same session.
 
 ``--group G`` (turns the regions stage on) adds the ``blocks`` stage (tsii_text_blocks, right behind the regions stage, which then labels
 every region and leaves the filter to the blocks): its own pair of events.  ``regions`` then counts blocks in ``found`` / ``kept`` and
@@ -69,15 +74,23 @@ def blob_field(h, w, fraction, seed, rects=None):
     return page
 
 
-def bubble_page(h, w, rects, share, seed, margin=16):
+def bubble_page(h, w, rects, share, seed, margin=16, ramps=False):
     """a noisy page; the first ``share`` of the blobs ``rects`` each on an ellipse of one colour that reaches ``margin`` pixels beyond the
-    blob's corners (later bubbles may cut into earlier ones, blobs may touch: the share of FLAT regions is what the run reports)"""
+    blob's corners (later bubbles may cut into earlier ones, blobs may touch: the share of FLAT regions is what the run reports).
+    ``ramps``: every ellipse carries a linear colour ramp instead, 60 grey levels from end to end along a direction of its own."""
     rng = np.random.default_rng(seed)
     page = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
     yy, xx = np.mgrid[0:h, 0:w]
     for y, x, bh, bw in rects[:int(round(share * len(rects)))]:
         ry, rx = (bh / 2 + margin) * 1.42, (bw / 2 + margin) * 1.42
-        page[((yy - (y + bh / 2)) / ry) ** 2 + ((xx - (x + bw / 2)) / rx) ** 2 <= 1.0] = rng.integers(180, 256, size=3, dtype=np.uint8)
+        inside = ((yy - (y + bh / 2)) / ry) ** 2 + ((xx - (x + bw / 2)) / rx) ** 2 <= 1.0
+        colour = rng.integers(180, 256, size=3, dtype=np.uint8)
+        if not ramps:
+            page[inside] = colour
+            continue
+        angle = rng.uniform(0.0, 2.0 * np.pi)
+        along = ((yy - (y + bh / 2)) * np.sin(angle) + (xx - (x + bw / 2)) * np.cos(angle)) / max(ry, rx)      # -1 .. 1 across the ellipse
+        page[inside] = np.clip(colour.astype(np.float64) - 30.0 + 30.0 * along[inside][:, None], 0, 255).astype(np.uint8)
     return page
 
 
@@ -111,6 +124,8 @@ def main(argv=None):
     ap.add_argument("--bubbles", type=float, default=None, metavar="SHARE", help="a noisy page with this share of the blobs on discs of one colour")
     ap.add_argument("--flat", type=int, default=None, metavar="T", help="time the flat stage (tsii_flat_regions) with this tolerance")
     ap.add_argument("--flat-ring", type=int, default=3)
+    ap.add_argument("--ramps", type=float, default=None, metavar="SHARE", help="--bubbles with a linear colour ramp on every ellipse")
+    ap.add_argument("--smooth", type=int, default=None, metavar="T", help="time the smooth stage (tsii_smooth_regions_* around tsii_harmonic_fill) with this tolerance")
     ap.add_argument("--group", type=int, default=None, metavar="G", help="time the blocks stage (tsii_text_blocks): regions within G pixels form a block")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
@@ -135,6 +150,8 @@ def main(argv=None):
     field = blob_field(h, w, 0.0 if args.all_text else args.text_fraction, 1, rects)
     if args.bubbles is not None:
         page = bubble_page(h, w, rects, args.bubbles, 2)
+    if args.ramps is not None:
+        page = bubble_page(h, w, rects, args.ramps, 2, ramps=True)
     if args.all_text:
         field.fill(4.0)
     if with_seg:                                          # the same text, sampled at the working size
@@ -142,13 +159,14 @@ def main(argv=None):
     logits_fixed = tile_logits(field, gs, dev)
     with_flat = args.flat is not None
     with_blocks = args.group is not None
-    with_regions = args.min_area > 0 or args.hull or args.pack or with_flat or with_blocks
+    with_smooth = args.smooth is not None
+    with_regions = args.min_area > 0 or args.hull or args.pack or with_flat or with_blocks or with_smooth
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
-                          flat=args.flat, flat_ring=args.flat_ring, group=args.group)
+                          flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -164,12 +182,14 @@ def main(argv=None):
         stages.append("hulls")                              # its own pair of events, right behind the regions (or blocks) stage
     if with_flat:
         stages.append("flat")                               # its own pair of events, behind the regions / hulls stages
+    if with_smooth:
+        stages.append("smooth")                             # its own pair of events, behind the flat stage
     if with_seg:
         stages += ["resize", "plane_up"]                    # their own pairs of events: behind the upload / behind the mask
 
     def one_page():
         marks = [ev() for _ in range(11)]
-        reg0, reg1, hul1, res1, up0, up1, fl0, fl1, blk1 = ev(), ev(), ev(), ev(), ev(), ev(), ev(), ev(), ev()
+        reg0, reg1, hul1, res1, up0, up1, fl0, fl1, blk1, sm0, sm1 = (ev() for _ in range(11))
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
@@ -202,11 +222,19 @@ def main(argv=None):
                     counts = eraser._hulls(text, g, counts)
                     hul1.record()
             src, split = page_d, 0                          # src: the page the filler and compose see
-            if with_flat:
+            if with_flat or with_smooth:                    # the second labelling behind the hulls is timed with the first stage that needs it
                 page_mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
-                fl0.record()
-                counts, split, src = eraser._flat(page_d, text, g, counts, page_mask)
-                fl1.record()
+                (fl0 if with_flat else sm0).record()
+                route = eraser._route_labels(text, g, counts)
+                if with_flat:
+                    src = eraser._flat(page_d, text, g, route, page_mask)
+                    fl1.record()
+                    sm0.record()
+                if with_smooth:
+                    src = eraser._smooth(src, text, g, route, None if with_flat else page_mask)
+                    sm1.record()
+                split = route[2]
+                counts = torch.cat([counts, route[1]]) if split else route[1]
             if with_blocks:                                 # members and the component count ride at the end, as in the eraser
                 counts = whole if counts is blocks[0] else torch.cat([counts, whole[int(blocks[0].numel()):]])
             marks[4].record()
@@ -226,14 +254,21 @@ def main(argv=None):
                 if args.hull:
                     region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h[:split] if split else packed_h, g.count, args.max_regions,
                                                                          len(table)).sum(dtype=np.int64))
-                if with_flat:                               # everything behind works on the flat stage's own components and counts
+                if with_flat or with_smooth:                # everything behind works on these stages' own components and counts
                     own = packed_h[split:]
                     packed_h = packed_h[:split] if split else packed_h
                     counts_h, ftable, _, _, truncated = RG.unpack_regions(own, g.count, args.max_regions)
-                    is_flat = RG.unpack_flat(own, g.count, args.max_regions, len(ftable))[0]
-                    region_info.update(labelled=len(ftable), flat_regions=int(is_flat.sum()),
-                                       flat_pixels=int(ftable[is_flat, 1].sum(dtype=np.int64)))
-                    table = ftable[~is_flat]
+                    gone, at = np.zeros(len(ftable), bool), g.count + 2 + 6 * args.max_regions
+                    region_info.update(labelled=len(ftable))
+                    if with_flat:
+                        is_flat = RG.unpack_flat(own, g.count, args.max_regions, len(ftable))[0]
+                        region_info.update(flat_regions=int(is_flat.sum()), flat_pixels=int(ftable[is_flat, 1].sum(dtype=np.int64)))
+                        gone, at = gone | is_flat, at + 5 * args.max_regions
+                    if with_smooth:
+                        is_smooth = RG.unpack_smooth(own[at:], len(ftable))[0]
+                        region_info.update(smooth_regions=int(is_smooth.sum()), smooth_pixels=int(ftable[is_smooth, 1].sum(dtype=np.int64)))
+                        gone = gone | is_smooth
+                    table = ftable[~gone]
             selected = [t for t in range(g.count) if counts_h[t] > 0]
             windows, plan_ms = None, 0.0
             if args.pack:
@@ -280,6 +315,8 @@ def main(argv=None):
             t.append((blk1 if with_blocks else reg1).elapsed_time(hul1))
         if with_flat:
             t.append(fl0.elapsed_time(fl1))
+        if with_smooth:
+            t.append(sm0.elapsed_time(sm1))
         if with_seg:
             t[1] = res1.elapsed_time(marks[2])
             t[3] = marks[3].elapsed_time(up0)
@@ -288,7 +325,16 @@ def main(argv=None):
 
     for _ in range(args.warmup):
         one_page()
+    split_names = ["tsii_smooth_regions_classify", "tsii_harmonic_fill", "tsii_smooth_regions_apply"]
+    if with_smooth and args.filler == "net":                # event pairs around the three calls of the smooth stage (_lib.start_timing)
+        from text_segmentation_image_inpainting_amd import _lib
+        _lib.start_timing(split_names)
     runs = [one_page() for _ in range(args.repeats)]
+    smooth_split = None
+    if with_smooth and args.filler == "net":
+        rec = _lib.stop_timing()
+        smooth_split = {n: {"median": round(statistics.median(v[0] for v in rec[n]), 4), "min": round(min(v[0] for v in rec[n]), 4),
+                            "max": round(max(v[0] for v in rec[n]), 4)} for n in split_names}
     n_sel, n_text, keep, windows = runs[0][1], runs[0][2], runs[0][3], runs[0][6]
     n_fill = n_sel if windows is None else len(windows[0])
     if windows is not None:                                 # the same two slots of the timeline, other kernels
@@ -317,6 +363,8 @@ def main(argv=None):
     if with_flat:                           # DESIGN.md, "flat regions": ring 1 (text) + apron, apply 3 + 1 in, 3 + 1 + 1 out, labels on the text
         apron = (64 + 2 * args.flat_ring) * (32 + 2 * args.flat_ring) / 2048.0
         bytes_["flat"] = int(apron * npx) + 9 * npx + 8 * int(runs[0][5]["flat_pixels"] + n_text) + (18 * npx if args.hull else 0)
+    if with_smooth:                         # DESIGN.md, "smooth regions": stage 4 in + 16 out, ring 1 + 3 (+ aprons), the solver 2.1 x (12 + 4) in
+        bytes_["smooth"] = 20 * npx + 4 * npx + int(2.1 * 16 * npx) + 12 * npx + 9 * npx      # + 12 out, apply 3 + 1 in, 3 + 1 + 1 out
 
     def timed(fn, sync=True):
         for _ in range(args.warmup):
@@ -435,6 +483,7 @@ def main(argv=None):
         "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
         "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
         "bubbles": args.bubbles, "flat": args.flat, "flat_ring": args.flat_ring if with_flat else None, "group": args.group,
+        "ramps": args.ramps, "smooth": args.smooth, "smooth_split_ms": smooth_split,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
