@@ -22,6 +22,9 @@ T grey levels -- lettering in a speech bubble -- with that colour on the device;
 ``--smooth T`` (0..255) fills the text regions whose surroundings (``--smooth-ring N`` pixels around them, default 3) show no step of more
 than T grey levels between neighbouring pixels -- lettering on a gradient, a soft shadow, a sky -- with the harmonic continuation of those
 surroundings (``--smooth-sweeps N``, default 8), behind ``--flat``; text over screentone or artwork still goes to the inpainting net.
+``--tone T`` (0..255) fills the text regions whose surroundings (``--tone-ring N`` pixels around them, default 8) are a pattern that repeats
+under one shift of 2..``--tone-period N`` (default 12) pixels within T grey levels -- lettering on screentone, stripes, a dot lattice --
+by copying the pixel a whole number of periods away, behind ``--smooth``.  The period must be a whole number of pixels.
 ``--filler harmonic`` needs no inpainting checkpoint: the holes take the smooth continuation of their surroundings (``T.HarmonicFill``,
 ``--sweeps N`` Jacobi sweeps per level, default 8), the right fill for text on a gradient, a soft shadow or a sky; no inpainting net is
 built or loaded.
@@ -76,6 +79,9 @@ def main(argv=None):
     ap.add_argument("--smooth", type=int, default=None, metavar="T", help="fill text regions harmonically whose surroundings step by at most T grey levels")
     ap.add_argument("--smooth-ring", type=int, default=3, metavar="N", help="width of the ring of surrounding pixels --smooth looks at (1..8)")
     ap.add_argument("--smooth-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of the --smooth fill (0..16)")
+    ap.add_argument("--tone", type=int, default=None, metavar="T", help="copy-fill text regions whose surroundings repeat under one shift within T grey levels")
+    ap.add_argument("--tone-ring", type=int, default=8, metavar="N", help="width of the ring of surrounding pixels --tone looks at (1..16)")
+    ap.add_argument("--tone-period", type=int, default=12, metavar="N", help="the longest period along each axis --tone looks for (2..16)")
     ap.add_argument("--group", type=int, default=None, metavar="G", help="group text regions within G pixels (1..64) into blocks: --min-area, --hull, "
                     "--flat and --pack then work per block, --boxes draws the block boxes")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: fill the holes with T.HarmonicFill, without an inpainting net")
@@ -96,7 +102,8 @@ def main(argv=None):
     eraser = T.TextEraser(nets[0], nets[1], tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
                           seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group,
-                          smooth=args.smooth, smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps)
+                          smooth=args.smooth, smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
+                          tone_period=args.tone_period)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -136,6 +143,8 @@ def main(argv=None):
             print("%s: %d flat text regions (%d pixels) painted without the inpainting net" % (name, st["flat_regions"], st["flat_pixels"]))
         if args.smooth is not None:
             print("%s: %d smooth text regions (%d pixels) filled harmonically without the inpainting net" % (name, st["smooth_regions"], st["smooth_pixels"]))
+        if args.tone is not None:
+            print("%s: %d tone text regions (%d pixels) filled from one period away without the inpainting net" % (name, st["tone_regions"], st["tone_pixels"]))
         if "seg_size" in st:
             print("%s: segmented at %d x %d (%d tiles)" % ((name,) + tuple(st["seg_size"]) + (st["seg_tiles"],)))
     print("Runtime :{:.3f} s -> {}".format(time.time() - t0, out_folder))

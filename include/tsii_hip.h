@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 15
+#define TSII_ABI_VERSION 16
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -875,6 +875,50 @@ int tsii_smooth_regions_classify(const uint8_t* page, const uint8_t* text, const
 int tsii_smooth_regions_apply(const uint8_t* page, uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
                               int max_regions, const int* smooth, const float* filled, int tile, int halo, int* core_count,
                               uint8_t* painted, uint8_t* mask, void* stream);
+
+/* ---- K17: tone regions (csrc/tone.hip) -- the third net-free route, behind K13 and K16: a text region whose surrounding RING of page
+ * pixels is a PERIODIC PATTERN (screentone, stripes, a dot lattice) is filled by copying, for each of its pixels, the nearest non-text
+ * pixel a whole number of periods away, and leaves the text plane.  One integer shift per region, measured on the ring.  All in 32-bit
+ * integers: exact, the same bits on every run.
+ * Inputs as K16 takes them: page uint8 [h,w,3]; text uint8 [h,w] (non-zero = text; REWRITTEN IN PLACE); labels int32 [h,w], table int32
+ * [max_regions,6] and n_regions int32 [2] ON THE DEVICE exactly as tsii_text_regions or tsii_text_blocks left them; ring 1..16; period
+ * 2..16; tol 0..255.  Only the label column of the table is read.  R = min(n_regions[1], max_regions); for r < R:
+ *   C_r      K16's: the pixels whose label is table[r][0] AND whose text byte is non-zero on entry (empty for a region K13 or K16 took)
+ *   Ring_r   K13's ring of width `ring`: the pixels q with text[q] == 0 on entry within `ring` (Chebyshev) of a pixel of C_r.  n_r = |Ring_r|
+ *   S        the shifts (dy, dx) with 0 <= dy <= period, |dx| <= period and (dy > 0 or dx > 0): one of every pair s, -s
+ *   Pairs_r(s) the q in Ring_r for which q + s is on the page and has text == 0 on entry (q + s need not lie in the ring)
+ *   cnt_r(s) = |Pairs_r(s)|;  err_r(s) = the largest |page[q][c] - page[q + s][c]| over the pairs and the three channels, 0 without a pair
+ *   s is SUPPORTED iff 2 cnt_r(s) >= n_r
+ *   step_r   = max(err_r((0,1)), err_r((1,0))).  The region is TEXTURED iff step_r > tol: a flat or gently graded ring is no pattern; it
+ *            belongs to K13, K16 or a net and is never streak-filled here
+ *   s_r      among the CANDIDATES -- the s with max(|dy|, |dx|) >= 2 that are SUPPORTED with err_r(s) <= tol, and none at all where
+ *            n_r == 0 -- the one with the smallest key (err, dy*dy + dx*dx, dy, dx): the best match, then the shortest, then a fixed order.
+ *            The unit shifts are measured for step_r and never chosen
+ *   src(p)   for p in C_r: the first pixel of p + s_r, p - s_r, p + 2 s_r, p - 2 s_r, ... (k = 1..256) that is on the page with
+ *            text == 0 on entry; none within 256 steps each way: p has no source
+ *   tone_r   iff n_r >= 1, TEXTURED, a candidate exists and every pixel of C_r has a source.  Regions beyond the table are never tone
+ * Outputs:
+ *   painted, uint8 [h,w,3] (not the page itself): page[src(p)] on C_r where tone_r holds, the page byte everywhere else
+ *   text[p]  = 0 on the tone regions, 1 where it was non-zero otherwise, else 0
+ *   mask, uint8 [h,w] or NULL: 255 where text was non-zero ON ENTRY, else 0
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the text pixels of
+ *            the FINAL plane in each tile core
+ *   tone, int32 [max_regions,6]: row r < R = {tone_r, dy, dx, err_r(s_r), n_r, step_r}; dy = dx = err = 0 without a candidate; a row with a
+ *            shift, step_r > tol and tone_r = 0 is a region with a pixel without a source; the rows behind R are not touched
+ *   page, labels, table and n_regions are read only.
+ * No allocation, no host synchronisation, everything on the caller's stream; no grid-wide barrier and no waiting on another block; atomicAdd
+ * and atomicMax on 32-bit integers only.
+ * ws: tsii_tone_regions_ws_bytes(h, w, max_regions, period) bytes (0: refused), 4-byte aligned; it depends on those four only, needs
+ * nothing cleared beforehand and holds nothing a later call depends on.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1; h*w*3 > 2^31; max_regions < 1 (or max_regions * (period + 1) *
+ * (2 period + 1) >= 2^30); ring outside 1..16, period outside 2..16, tol outside 0..255; a NULL among page, text, labels, table, n_regions,
+ * painted, tone, ws; painted == page; a bad tile geometry while core_count != NULL.  The count read from n_regions is clamped to
+ * max_regions and every table row is found by a search below it; the boxes of the table are not read: a table that does not belong to the
+ * labels gives wrong bytes, never an access outside the buffers. */
+size_t tsii_tone_regions_ws_bytes(int h, int w, int max_regions, int period);
+int tsii_tone_regions(const uint8_t* page, uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
+                      int max_regions, int ring, int period, int tol, int tile, int halo, int* core_count,
+                      uint8_t* painted, uint8_t* mask, int* tone, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

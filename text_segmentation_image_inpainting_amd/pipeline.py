@@ -22,6 +22,9 @@ With ``smooth`` the regions whose surroundings are locally smooth -- lettering o
 harmonic continuation of those surroundings at page level (``csrc/smooth.hip``; "K16: smooth regions", around the solver of
 ``csrc/harmonic.hip``) and never reach the filler either: flat, then smooth, then the net, decided per region on the device.
 
+With ``tone`` the regions whose surroundings are a periodic pattern -- lettering on screentone, stripes, a dot lattice -- are filled by copying
+the pixel a whole number of periods away (``csrc/tone.hip``; "K17: tone regions"): flat, then smooth, then tone, then the net.
+
 With ``group`` the regions are first grouped into blocks of lettering on the device (``csrc/blocks.hip``; "K15: text blocks"): the area
 filter, the hulls, the flat stage and ``pack`` then judge, fill, paint and place whole blocks instead of single glyphs.
 """
@@ -36,8 +39,9 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import (_flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, check_block_args, check_flat_args,
-                      check_region_args, check_smooth_args, unpack_blocks, unpack_flat, unpack_hull_area, unpack_regions, unpack_smooth)
+from .regions import (_flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args,
+                      check_flat_args, check_region_args, check_smooth_args, check_tone_args, unpack_blocks, unpack_flat, unpack_hull_area,
+                      unpack_regions, unpack_smooth, unpack_tone)
 
 
 class TileGrid(NamedTuple):
@@ -326,6 +330,17 @@ class TextEraser:
     ``step`` (uint8 ``[n, 3]``: the largest step between neighbours in each ring) and ``ring_pixels``.  Still one synchronisation.
     ``None`` (the default): none of this runs.
 
+    ``tone=T`` (an integer 0..255; turns the regions path on as well): the third route without a net, behind ``flat`` and ``smooth``.  A text
+    region is TONE when its ring -- ``tone_ring`` (1..16) wide -- is textured (two neighbouring pixels differ by more than ``T`` somewhere)
+    and repeats under one shift of 2..``tone_period`` (2..16) pixels along each axis: at least half the ring has a partner that is not
+    text under the shift and no such pair differs by more than ``T`` grey levels in any channel.  Every pixel of such a region is filled
+    with the nearest pixel that is not text a whole number of shifts away, on the page the earlier stages painted (what they filled is a
+    valid source); the region selects no tile, is no hole for the filler and is not among the boxes ``pack`` places its windows on; a
+    page whose text is all flat, smooth or tone never calls the filler.  The period must be a whole number of pixels at the page's
+    resolution; the error is a maximum, so one outlier in the ring rejects a shift; there is one shift per region.  ``last_stats`` gains
+    ``tone_regions`` and ``tone_pixels``, ``last_regions`` gains ``tone``: a dict of ``table``, ``is_tone``, ``shift`` (int32 ``[n, 2]``),
+    ``err``, ``step`` and ``ring_pixels``.  Still one synchronisation.  ``None`` (the default): none of this runs.
+
     ``group=G`` (an integer 1..64; turns the regions path on as well): the connected regions are grouped into BLOCKS first -- two regions
     are in one block when some pixel of one is within ``G`` pixels (Chebyshev distance) of some pixel of the other, directly or through
     other regions: the lines of a speech bubble with a ``G`` of about the line spacing -- and everything behind works on blocks:
@@ -344,7 +359,7 @@ class TextEraser:
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
                  max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
-                 smooth_ring=3, smooth_sweeps=8):
+                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -369,8 +384,11 @@ class TextEraser:
         if smooth is not None or smooth_ring != 3 or smooth_sweeps != 8:
             check_smooth_args(0 if smooth is None else smooth, smooth_ring, smooth_sweeps)
         self.smooth, self.smooth_ring, self.smooth_sweeps = None if smooth is None else int(smooth), int(smooth_ring), int(smooth_sweeps)
-        self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.flat is not None or self.group is not None
-                        or self.smooth is not None)
+        if tone is not None or tone_ring != 8 or tone_period != 12:
+            check_tone_args(0 if tone is None else tone, tone_ring, tone_period)
+        self.tone, self.tone_ring, self.tone_period = None if tone is None else int(tone), int(tone_ring), int(tone_period)
+        self.routes = self.flat is not None or self.smooth is not None or self.tone is not None
+        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -382,8 +400,8 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks"; + "smooth_regions", "smooth_pixels")
-        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components"; + "smooth")
+        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks"; + "smooth_regions", "smooth_pixels"; + "tone_regions", "tone_pixels")
+        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components"; + "smooth"; + "tone")
         self.last_labels = None                         # its int32 label plane, left on the device
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
@@ -425,8 +443,9 @@ class TextEraser:
         return self.max_regions if self.hull else self._route_tail()
 
     def _route_tail(self):
-        """the words behind the table of the labelling the flat and smooth stages work on: 5 per row and stage, flat rows first"""
-        return 5 * self.max_regions * ((self.flat is not None) + (self.smooth is not None))
+        """the words behind the table of the labelling the flat, smooth and tone stages work on: 5 per row for flat, 5 for smooth, 6 for
+        tone, in that order"""
+        return self.max_regions * (5 * ((self.flat is not None) + (self.smooth is not None)) + 6 * (self.tone is not None))
 
     def _blocks(self, text, g, packed):
         """group the labelled regions into blocks and filter those, in place -> (the blocks' [core counts | found, kept | table], in the
@@ -442,8 +461,8 @@ class TextEraser:
         return packed
 
     def _route_labels(self, text, g, packed):
-        """what the flat and smooth stages work on -> (labels, ONE device tensor ``[core counts | found, kept | table | flat rows | smooth
-        rows]``, the number of words of ``packed`` that ride in front of it in the read-back).  Behind the hulls the filled plane is
+        """what the flat, smooth and tone stages work on -> (labels, ONE device tensor ``[core counts | found, kept | table | flat rows |
+        smooth rows | tone rows]``, the number of words of ``packed`` that ride in front of it in the read-back).  Behind the hulls the filled plane is
         labelled once more, for both stages (hull pixels carry no label), and that call's tensor rides behind ``packed``; otherwise the
         rows are the tail of ``packed`` itself and nothing rides in front."""
         if self.hull:
@@ -469,6 +488,19 @@ class TextEraser:
         painted = torch.empty_like(src)
         _smooth_regions(src, text, labels, own[g.count + 2:], own[g.count:g.count + 2], own[at:at + 5 * n], n, self.smooth_ring, self.smooth,
                         self.smooth_sweeps, painted, mask_u8, g, own[:g.count])
+        return painted
+
+    def _tone(self, src, text, g, route, mask_u8):
+        """fill the tone regions from one period away and take them out of the text plane in place -> the filled page (a new buffer;
+        ``src``: the page, or the stage's before).  ``mask_u8``: the plane that gets the mask of the whole plane on entry, None where an
+        earlier stage wrote the page's already.  The tone rows ride behind the flat and smooth rows of ``route``'s tensor, the core counts
+        at its front are rewritten for the reduced plane."""
+        labels, own, _ = route
+        n = self.max_regions
+        at = g.count + 2 + 6 * n + 5 * n * ((self.flat is not None) + (self.smooth is not None))
+        painted = torch.empty_like(src)
+        _tone_regions(src, text, labels, own[g.count + 2:], own[g.count:g.count + 2], own[at:at + 6 * n], n, self.tone_ring, self.tone_period,
+                      self.tone, painted, mask_u8, g, own[:g.count])
         return painted
 
     def _run_filler(self, img, mplane, g):
@@ -532,12 +564,14 @@ class TextEraser:
                     counts, whole = blocks = self._blocks(text, g, counts)
                 if self.hull:
                     counts = self._hulls(text, g, counts)
-                if self.flat is not None or self.smooth is not None:
+                if self.routes:
                     route = self._route_labels(text, g, counts)
-                    if self.flat is not None:           # the first of the two stages writes the page's mask; compose's, of the reduced plane, is scratch
+                    if self.flat is not None:           # the first of the stages writes the page's mask; compose's, of the reduced plane, is scratch
                         src = self._flat(page_d, text, g, route, mask_u8)
                     if self.smooth is not None:
                         src = self._smooth(src, text, g, route, None if self.flat is not None else mask_u8)
+                    if self.tone is not None:
+                        src = self._tone(src, text, g, route, None if src is not page_d else mask_u8)
                     compose_mask = torch.empty_like(mask_u8)
                     split = route[2]
                     counts = torch.cat([counts, route[1]]) if split else route[1]
@@ -545,7 +579,7 @@ class TextEraser:
                     ride = int(blocks[0].numel())
                     counts = whole if counts is blocks[0] else torch.cat([counts, whole[ride:]])
             counts_h = all_h = counts.cpu().numpy()     # the one synchronisation before the download
-            flat_pixels = smooth_pixels = 0
+            flat_pixels = smooth_pixels = tone_pixels = 0
             if self.regions:
                 if self.group is not None:
                     all_h, blocks_h = all_h[:-(self.max_regions + 1)], all_h[-(self.max_regions + 1):]
@@ -557,7 +591,7 @@ class TextEraser:
                     self.last_regions.update(members=members, components=components)
                 if self.hull:
                     self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
-                if self.flat is not None or self.smooth is not None:
+                if self.routes:
                     packed_h = all_h[split:]            # behind the hulls: the filled plane's own components; all that follows works on them
                     counts_h, ftable, _, _, ftruncated = unpack_regions(packed_h, g.count, self.max_regions)
                     gone, at = np.zeros(len(ftable), bool), g.count + 2 + 6 * self.max_regions
@@ -570,7 +604,13 @@ class TextEraser:
                         is_smooth, step, ring_pixels = unpack_smooth(packed_h[at:], len(ftable))
                         self.last_regions["smooth"] = {"table": ftable, "is_smooth": is_smooth, "step": step, "ring_pixels": ring_pixels}
                         smooth_pixels = int(ftable[is_smooth, 1].sum(dtype=np.int64))
-                        gone = gone | is_smooth
+                        gone, at = gone | is_smooth, at + 5 * self.max_regions
+                    if self.tone is not None:           # a flat or smooth region has no text left: its tone row is empty
+                        is_tone, shift, err, step, ring_pixels = unpack_tone(packed_h[at:], len(ftable))
+                        self.last_regions["tone"] = {"table": ftable, "is_tone": is_tone, "shift": shift, "err": err, "step": step,
+                                                     "ring_pixels": ring_pixels}
+                        tone_pixels = int(ftable[is_tone, 1].sum(dtype=np.int64))
+                        gone = gone | is_tone
                     table, truncated = ftable[~gone], ftruncated        # what pack plans its windows on
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
@@ -584,13 +624,15 @@ class TextEraser:
             else:
                 _compose_page_u8(src, text, out, slot, g, clean, compose_mask)
         self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0,
-                           "text_pixels": int(counts_h.sum()) + flat_pixels + smooth_pixels}
+                           "text_pixels": int(counts_h.sum()) + flat_pixels + smooth_pixels + tone_pixels}
         if self.group is not None:
             self.last_stats.update(blocks=self.last_regions["kept"])
         if self.flat is not None:
             self.last_stats.update(flat_regions=int(is_flat.sum()), flat_pixels=flat_pixels)
         if self.smooth is not None:
             self.last_stats.update(smooth_regions=int(is_smooth.sum()), smooth_pixels=smooth_pixels)
+        if self.tone is not None:
+            self.last_stats.update(tone_regions=int(is_tone.sum()), tone_pixels=tone_pixels)
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)

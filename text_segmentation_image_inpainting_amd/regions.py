@@ -17,6 +17,10 @@ whose ring shows no step of more than a tolerance between neighbouring pixels is
 surroundings at page level (``tsii_smooth_regions_classify`` / ``tsii_smooth_regions_apply``, ``csrc/smooth.hip``; "K16: smooth regions",
 around the ``tsii_harmonic_fill`` of ``fill.py``) and leaves the plane.
 
+``tone_fill_regions`` is the third route without a net, for text on a periodic pattern (screentone, stripes, a dot lattice): a region
+whose ring repeats under one integer shift is filled by copying the pixel a whole number of periods away (``tsii_tone_regions``,
+``csrc/tone.hip``; "K17: tone regions") and leaves the plane.
+
 ``text_blocks`` groups the regions into blocks of lettering: two regions belong together when some pixel of one is within ``gap`` pixels
 (Chebyshev distance) of some pixel of the other, and so on through their neighbours (``tsii_text_blocks``, ``csrc/blocks.hip``; "K15:
 text blocks").  The block labels and the block table have the form of the regions' own, so the hulls, the flat stage and the window
@@ -61,6 +65,22 @@ class SmoothFill(NamedTuple):
     text: object
     table: np.ndarray
     is_smooth: np.ndarray
+    step: np.ndarray
+    ring_pixels: np.ndarray
+
+
+class ToneFill(NamedTuple):
+    """``painted``: uint8 ``[H, W, 3]``, the page with every tone region filled from one period away.  ``text``: uint8 ``[H, W]`` of 0 / 255,
+    the text that is left for a net.  ``table``: numpy int32 ``[n, 6]``, the region table (``TextRegions.table``).  Per table row:
+    ``is_tone`` (numpy bool ``[n]``), ``shift`` (int32 ``[n, 2]``: ``dy, dx`` of the ring's period, 0 0 without one), ``err`` (int32
+    ``[n]``: the largest difference under that shift), ``step`` (int32 ``[n]``: the largest difference under a shift of one pixel) and
+    ``ring_pixels`` (int32 ``[n]``)."""
+    painted: object
+    text: object
+    table: np.ndarray
+    is_tone: np.ndarray
+    shift: np.ndarray
+    err: np.ndarray
     step: np.ndarray
     ring_pixels: np.ndarray
 
@@ -122,6 +142,15 @@ def check_smooth_args(tol, ring, sweeps):
         check_sweeps(sweeps)
     except ValueError as e:
         raise ValueError(f"smooth {e}") from None
+
+
+def check_tone_args(tol, ring, period):
+    if isinstance(tol, bool) or int(tol) != tol or not 0 <= tol <= 255:
+        raise ValueError(f"tone tolerance {tol} must be an integer 0..255")
+    if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 16:
+        raise ValueError(f"tone ring {ring} must be an integer 1..16")
+    if isinstance(period, bool) or int(period) != period or not 2 <= period <= 16:
+        raise ValueError(f"tone period {period} must be an integer 2..16")
 
 
 def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
@@ -234,6 +263,32 @@ def _smooth_regions(page, text, labels, table, n_regions, rows, max_regions, rin
          ptr(core_count) if grid is not None else None, ptr(painted), ptr(mask), _lib.stream())
 
 
+def _tone_regions(page, text, labels, table, n_regions, rows, max_regions, ring, period, tol, painted, mask=None, grid=None, core_count=None):
+    """``tsii_tone_regions`` on the current stream, in place on the device plane ``text``: ``labels``, ``table`` (the device words of the
+    table) and ``n_regions`` (the device pair) as the labelling -- or the flat and smooth stages behind it -- left them; ``rows``:
+    ``6 * max_regions`` device words for the tone rows; ``core_count`` (with ``grid``) is rewritten for the reduced plane.  ``painted`` (and
+    ``mask``, the 0 / 255 plane of the text on entry) are written."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    n = int(max_regions)
+    assert rows.numel() == 6 * n and rows.dtype == torch.int32 and rows.device == text.device and rows.is_contiguous()
+    assert page.shape == (h, w, 3) and painted.shape == (h, w, 3) and all(t.dtype == torch.uint8 and t.is_contiguous() for t in (page, painted, text))
+    assert mask is None or (mask.shape == (h, w) and mask.dtype == torch.uint8 and mask.is_contiguous())
+    nbytes = int(_lib.lib().tsii_tone_regions_ws_bytes(h, w, n, int(period)))
+    if nbytes == 0:
+        raise ValueError(f"text plane of {h} x {w} pixels, {n} regions, period {period}: out of range")
+    ws = ops._ws(nbytes, text)
+    tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
+    call("tsii_tone_regions", ptr(page), ptr(text), ptr(labels), h, w, ptr(table), ptr(n_regions), n, int(ring), int(period), int(tol), tile, halo,
+         ptr(core_count) if grid is not None else None, ptr(painted), ptr(mask), ptr(rows), ptr(ws), _lib.stream())
+
+
+def unpack_tone(rows_h, n):
+    """host copy of the tone rows -> (is_tone bool ``[n]``, shift int32 ``[n, 2]``, err, step, ring_pixels int32 ``[n]``) of the ``n`` table
+    rows in use"""
+    rows = rows_h[:6 * n].reshape(n, 6)
+    return rows[:, 0] != 0, rows[:, 1:3].copy(), rows[:, 3].copy(), rows[:, 5].copy(), rows[:, 4].copy()
+
+
 def unpack_smooth(rows_h, n):
     """host copy of the smooth rows -> (is_smooth bool ``[n]``, step uint8 ``[n, 3]``, ring_pixels int32 ``[n]``) of the ``n`` table rows
     in use"""
@@ -344,6 +399,35 @@ def smooth_fill_regions(page_u8, mask_u8, tol, ring=3, sweeps=8, connectivity=8,
     _, table, _, _, _ = unpack_regions(packed_h, 0, n)
     is_smooth, step, ring_pixels = unpack_smooth(packed_h[2 + 6 * n:], len(table))
     return SmoothFill(_like(painted, page_u8), _like(plane * 255, mask_u8), table, is_smooth, step, ring_pixels)
+
+
+def tone_fill_regions(page_u8, mask_u8, tol, ring=8, period=12, connectivity=8, min_area=0, max_regions=4096, device=None) -> ToneFill:
+    """Fill the text that sits on a periodic pattern.  ``page_u8``: ``[H, W, 3]`` uint8; ``mask_u8``: ``[H, W]`` uint8, non-zero = text (the
+    255 masks ``TextEraser`` returns work directly); numpy or torch, host or device, neither is modified.  Regions below ``min_area`` are
+    dropped first, as in ``text_regions``.  The ring of a kept region -- the page pixels within ``ring`` (1..16, Chebyshev distance) of it
+    that are not text themselves -- is compared with the page under every shift of up to ``period`` (2..16) pixels along each axis.  The
+    region is TONE when the ring is textured (two neighbouring pixels differ by more than ``tol`` somewhere), when under some shift of two
+    pixels or more at least half the ring has a non-text partner and no such pair differs by more than ``tol`` (0..255) in any channel --
+    the best such shift, then the shortest, is the region's period -- and when every text pixel of the region reaches a non-text pixel
+    within 256 periods either way.  It is filled with those pixels and leaves ``text``.  The period must be a whole number of pixels;
+    one outlier in the ring rejects a shift.  Regions without a ring, and kept regions beyond ``max_regions``, are never tone.
+    ``painted`` comes back the same kind and on the same device as ``page_u8``, ``text`` as ``mask_u8``; one synchronisation (the
+    read-back of the counts, the table and the tone rows).  Host arguments are computed on ``device`` (default ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_tone_args(tol, ring, period)
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
+        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
+    plane = _plane_on_device(mask_u8, device)
+    page = p.to(plane.device).contiguous()
+    n = int(max_regions)
+    labels, packed = _text_regions(plane, connectivity, min_area, n, tail=6 * n)
+    painted = torch.empty_like(page)
+    _tone_regions(page, plane, labels, packed[2:], packed[:2], packed[2 + 6 * n:], n, ring, period, tol, painted)
+    packed_h = packed.cpu().numpy()
+    _, table, _, _, _ = unpack_regions(packed_h, 0, n)
+    is_tone, shift, err, step, ring_pixels = unpack_tone(packed_h[2 + 6 * n:], len(table))
+    return ToneFill(_like(painted, page_u8), _like(plane * 255, mask_u8), table, is_tone, shift, err, step, ring_pixels)
 
 
 def text_blocks(mask_u8, gap, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextBlocks:

@@ -3,7 +3,7 @@
 
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
                                 [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
-                                [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T]
+                                [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T] [--tones SHARE] [--tone T [--tone-ring N] [--tone-period N]]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
@@ -40,6 +40,10 @@ stage on) adds the ``smooth`` stage (tsii_smooth_regions_classify, tsii_harmonic
 the flat stage; with its own pair of events, and, with the net as the filler, split into its three calls by events around each:
 ``smooth_split_ms``).  Compare with a run on the same ``--ramps`` page without ``--smooth`` in the same session.
 
+``--tones SHARE`` is ``--bubbles`` with a dot lattice on every ellipse instead of one colour (period 6 along both axes, every other row of
+dots offset by 3); ``--tone T`` (turns the regions stage on) adds the ``tone`` stage (tsii_tone_regions, behind the smooth stage) with its
+own pair of events and reports the tone regions.  Compare with a run on the same ``--tones`` page without ``--tone`` in the same session.
+
 ``--group G`` (turns the regions stage on) adds the ``blocks`` stage (tsii_text_blocks, right behind the regions stage, which then labels
 every region and leaves the filter to the blocks): its own pair of events.  ``regions`` then counts blocks in ``found`` / ``kept`` and
 reports ``components`` and ``largest_block`` (members).  Compare with the same line without ``--group`` in the same session.
@@ -74,10 +78,12 @@ def blob_field(h, w, fraction, seed, rects=None):
     return page
 
 
-def bubble_page(h, w, rects, share, seed, margin=16, ramps=False):
+def bubble_page(h, w, rects, share, seed, margin=16, ramps=False, tones=False):
     """a noisy page; the first ``share`` of the blobs ``rects`` each on an ellipse of one colour that reaches ``margin`` pixels beyond the
     blob's corners (later bubbles may cut into earlier ones, blobs may touch: the share of FLAT regions is what the run reports).
-    ``ramps``: every ellipse carries a linear colour ramp instead, 60 grey levels from end to end along a direction of its own."""
+    ``ramps``: every ellipse carries a linear colour ramp instead, 60 grey levels from end to end along a direction of its own.
+    ``tones``: every ellipse carries a dot lattice instead: dots of 2 x 2 pixels 60 grey levels darker, period 6 along both axes, every
+    other row of dots offset by 3 (the lattice vectors (3, 3) and (0, 6))."""
     rng = np.random.default_rng(seed)
     page = rng.integers(0, 256, size=(h, w, 3), dtype=np.uint8)
     yy, xx = np.mgrid[0:h, 0:w]
@@ -85,6 +91,11 @@ def bubble_page(h, w, rects, share, seed, margin=16, ramps=False):
         ry, rx = (bh / 2 + margin) * 1.42, (bw / 2 + margin) * 1.42
         inside = ((yy - (y + bh / 2)) / ry) ** 2 + ((xx - (x + bw / 2)) / rx) ** 2 <= 1.0
         colour = rng.integers(180, 256, size=3, dtype=np.uint8)
+        if tones:
+            dots = ((yy % 6 < 2) & (xx % 6 < 2)) | (((yy + 3) % 6 < 2) & ((xx + 3) % 6 < 2))
+            page[inside] = colour
+            page[inside & dots] = colour - 60
+            continue
         if not ramps:
             page[inside] = colour
             continue
@@ -126,6 +137,10 @@ def main(argv=None):
     ap.add_argument("--flat-ring", type=int, default=3)
     ap.add_argument("--ramps", type=float, default=None, metavar="SHARE", help="--bubbles with a linear colour ramp on every ellipse")
     ap.add_argument("--smooth", type=int, default=None, metavar="T", help="time the smooth stage (tsii_smooth_regions_* around tsii_harmonic_fill) with this tolerance")
+    ap.add_argument("--tones", type=float, default=None, metavar="SHARE", help="--bubbles with a dot lattice on every ellipse")
+    ap.add_argument("--tone", type=int, default=None, metavar="T", help="time the tone stage (tsii_tone_regions) with this tolerance")
+    ap.add_argument("--tone-ring", type=int, default=8)
+    ap.add_argument("--tone-period", type=int, default=12)
     ap.add_argument("--group", type=int, default=None, metavar="G", help="time the blocks stage (tsii_text_blocks): regions within G pixels form a block")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
@@ -152,6 +167,8 @@ def main(argv=None):
         page = bubble_page(h, w, rects, args.bubbles, 2)
     if args.ramps is not None:
         page = bubble_page(h, w, rects, args.ramps, 2, ramps=True)
+    if args.tones is not None:
+        page = bubble_page(h, w, rects, args.tones, 2, tones=True)
     if args.all_text:
         field.fill(4.0)
     if with_seg:                                          # the same text, sampled at the working size
@@ -160,13 +177,16 @@ def main(argv=None):
     with_flat = args.flat is not None
     with_blocks = args.group is not None
     with_smooth = args.smooth is not None
-    with_regions = args.min_area > 0 or args.hull or args.pack or with_flat or with_blocks or with_smooth
+    with_tone = args.tone is not None
+    with_routes = with_flat or with_smooth or with_tone
+    with_regions = args.min_area > 0 or args.hull or args.pack or with_blocks or with_routes
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
-                          flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth)
+                          flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth, tone=args.tone,
+                          tone_ring=args.tone_ring, tone_period=args.tone_period)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -184,12 +204,14 @@ def main(argv=None):
         stages.append("flat")                               # its own pair of events, behind the regions / hulls stages
     if with_smooth:
         stages.append("smooth")                             # its own pair of events, behind the flat stage
+    if with_tone:
+        stages.append("tone")                               # its own pair of events, behind the smooth stage
     if with_seg:
         stages += ["resize", "plane_up"]                    # their own pairs of events: behind the upload / behind the mask
 
     def one_page():
         marks = [ev() for _ in range(11)]
-        reg0, reg1, hul1, res1, up0, up1, fl0, fl1, blk1, sm0, sm1 = (ev() for _ in range(11))
+        reg0, reg1, hul1, res1, up0, up1, fl0, fl1, blk1, sm0, sm1, tn0, tn1 = (ev() for _ in range(13))
         page_pinned = torch.from_numpy(page)
         with torch.no_grad():
             marks[0].record()
@@ -222,9 +244,9 @@ def main(argv=None):
                     counts = eraser._hulls(text, g, counts)
                     hul1.record()
             src, split = page_d, 0                          # src: the page the filler and compose see
-            if with_flat or with_smooth:                    # the second labelling behind the hulls is timed with the first stage that needs it
+            if with_routes:                                 # the second labelling behind the hulls is timed with the first stage that needs it
                 page_mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
-                (fl0 if with_flat else sm0).record()
+                (fl0 if with_flat else sm0 if with_smooth else tn0).record()
                 route = eraser._route_labels(text, g, counts)
                 if with_flat:
                     src = eraser._flat(page_d, text, g, route, page_mask)
@@ -233,6 +255,11 @@ def main(argv=None):
                 if with_smooth:
                     src = eraser._smooth(src, text, g, route, None if with_flat else page_mask)
                     sm1.record()
+                if with_tone:
+                    if with_flat or with_smooth:
+                        tn0.record()
+                    src = eraser._tone(src, text, g, route, None if (with_flat or with_smooth) else page_mask)
+                    tn1.record()
                 split = route[2]
                 counts = torch.cat([counts, route[1]]) if split else route[1]
             if with_blocks:                                 # members and the component count ride at the end, as in the eraser
@@ -254,7 +281,7 @@ def main(argv=None):
                 if args.hull:
                     region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h[:split] if split else packed_h, g.count, args.max_regions,
                                                                          len(table)).sum(dtype=np.int64))
-                if with_flat or with_smooth:                # everything behind works on these stages' own components and counts
+                if with_routes:                             # everything behind works on these stages' own components and counts
                     own = packed_h[split:]
                     packed_h = packed_h[:split] if split else packed_h
                     counts_h, ftable, _, _, truncated = RG.unpack_regions(own, g.count, args.max_regions)
@@ -267,7 +294,11 @@ def main(argv=None):
                     if with_smooth:
                         is_smooth = RG.unpack_smooth(own[at:], len(ftable))[0]
                         region_info.update(smooth_regions=int(is_smooth.sum()), smooth_pixels=int(ftable[is_smooth, 1].sum(dtype=np.int64)))
-                        gone = gone | is_smooth
+                        gone, at = gone | is_smooth, at + 5 * args.max_regions
+                    if with_tone:
+                        is_tone = RG.unpack_tone(own[at:], len(ftable))[0]
+                        region_info.update(tone_regions=int(is_tone.sum()), tone_pixels=int(ftable[is_tone, 1].sum(dtype=np.int64)))
+                        gone = gone | is_tone
                     table = ftable[~gone]
             selected = [t for t in range(g.count) if counts_h[t] > 0]
             windows, plan_ms = None, 0.0
@@ -317,6 +348,8 @@ def main(argv=None):
             t.append(fl0.elapsed_time(fl1))
         if with_smooth:
             t.append(sm0.elapsed_time(sm1))
+        if with_tone:
+            t.append(tn0.elapsed_time(tn1))
         if with_seg:
             t[1] = res1.elapsed_time(marks[2])
             t[3] = marks[3].elapsed_time(up0)
@@ -365,6 +398,10 @@ def main(argv=None):
         bytes_["flat"] = int(apron * npx) + 9 * npx + 8 * int(runs[0][5]["flat_pixels"] + n_text) + (18 * npx if args.hull else 0)
     if with_smooth:                         # DESIGN.md, "smooth regions": stage 4 in + 16 out, ring 1 + 3 (+ aprons), the solver 2.1 x (12 + 4) in
         bytes_["smooth"] = 20 * npx + 4 * npx + int(2.1 * 16 * npx) + 12 * npx + 9 * npx      # + 12 out, apply 3 + 1 in, 3 + 1 + 1 out
+    if with_tone:                           # DESIGN.md, "tone regions": ring 1 (text) + aprons per shift chunk, source 1 + 4, apply 3 + 1 in, 3 + 1 + 1 out
+        chunks = -(-((args.tone_period + 1) * (2 * args.tone_period + 1)) // 128)
+        apron = (64 + 2 * args.tone_ring) * (32 + 2 * args.tone_ring) / 2048.0
+        bytes_["tone"] = int(chunks * apron * npx) + npx + 9 * npx + 16 * int(runs[0][5]["tone_pixels"] + n_text)
 
     def timed(fn, sync=True):
         for _ in range(args.warmup):
@@ -484,6 +521,8 @@ def main(argv=None):
         "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
         "bubbles": args.bubbles, "flat": args.flat, "flat_ring": args.flat_ring if with_flat else None, "group": args.group,
         "ramps": args.ramps, "smooth": args.smooth, "smooth_split_ms": smooth_split,
+        "tones": args.tones, "tone": args.tone, "tone_ring": args.tone_ring if with_tone else None,
+        "tone_period": args.tone_period if with_tone else None,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
