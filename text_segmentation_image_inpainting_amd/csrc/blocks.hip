@@ -17,13 +17,10 @@
 //               and added to the block's statistics with one set of atomics per (rectangle, block);
 //   7. filter, scan, table: block_labels and text are rewritten by the area filter; counts and the table as in K10.
 // No grid-wide barrier, no waiting on another block: each step is its own launch.
+#include "emu_atomics.h"
 #include "region_bits.h"
 
 namespace tsii {
-
-#ifdef TSII_HIP_EMU
-static inline unsigned atomicMin(unsigned* p, unsigned v) { const unsigned o = *p; if (v < o) *p = v; return o; }
-#endif
 
 constexpr int BK_GAP_MAX = 64;
 constexpr int DL_WORDS = 4, DL_ROWS = 32;                    // the dilate kernel's rectangle: 256 x 32 pixels

@@ -4,41 +4,25 @@
 // bits on every run.
 //
 //   1. init:   the statistics of all max_regions table rows (nothing in ws has to be cleared by the caller);
-//   2. ring:   a block owns FL_W x FL_H page pixels and stages, for them and an apron of `ring` pixels, the table row of every text
-//              pixel (binary search over the ascending label column; labels are read for text pixels only).  A dilated bit mask of
-//              "has a row" (the construction of the K8 mask kernel) sends the great majority of non-text pixels away after one test; a
-//              non-text pixel next to text walks its (2 ring + 1)^2 window once per two distinct rows, lowest first.  A thread keeps
-//              the statistics of the row it met last in registers, rows meet per block in a small LDS hash table (a full table sends
-//              a thread's statistics to memory directly) and leave the block as one set of integer atomics per (block, row);
+//   2. ring:   the ring walk of region_ring.h: a block owns RING_W x RING_H page pixels and stages, for them and an apron of `ring`
+//              pixels, the table row of every text pixel (stage_rows); the dilated bit mask sends the great majority of non-text pixels
+//              away after one test (near_bits); a non-text pixel next to text meets the rows of its (2 ring + 1)^2 window lowest first
+//              (for_rows_in_window).  A thread keeps the statistics of the row it met last in registers, rows meet per block in a small
+//              LDS hash table (a full table sends a thread's statistics to memory directly) and leave the block as one set of integer
+//              atomics per (block, row);
 //   3. decide: one thread per table row: flat or not, the rounded mean colour, the ring's pixel count -> `flat`;
-//   4. apply:  a block owns a FL_W x FL_H rectangle of one tile core, a thread 4 consecutive pixels of a row: 12 page bytes and 4 text
+//   4. apply:  a block owns a RING_W x RING_H rectangle of one tile core, a thread 4 consecutive pixels of a row: 12 page bytes and 4 text
 //              bytes in, labels only where there is text; painted, text, mask out, one atomicAdd per block for the core count.
 // No grid-wide barrier, no waiting on another block: each step is its own launch.  The count read from n_regions is clamped to
 // max_regions and a row found by the search lies below it: a table that does not belong to the labels gives wrong bytes, never an
 // access outside the buffers.  The boxes of the table are not read.
-#include "page_grid.h"
-
-#include <limits.h>
-#include <string.h>
+#include "region_ring.h"
 
 namespace tsii {
 
-typedef unsigned long long u64;
-
-#ifdef TSII_HIP_EMU
-// the test emulator runs one thread at a time and supplies the 32-bit atomicAdd only
-static inline int atomicMin(int* p, int v) { const int o = *p; if (v < o) *p = v; return o; }
-static inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v; return o; }
-static inline int atomicCAS(int* p, int expect, int v) { const int o = *p; if (o == expect) *p = v; return o; }
-using ::atomicAdd;
-static inline u64 atomicAdd(u64* p, u64 v) { const u64 o = *p; *p = o + v; return o; }
-#endif
-
-constexpr int FL_W = 64, FL_H = 32, FL_THREADS = 256, FL_PER = FL_W * FL_H / FL_THREADS;
-constexpr int FL_RMAX = 8, FL_SW = FL_W + 2 * FL_RMAX, FL_SH = FL_H + 2 * FL_RMAX;      // the staged rectangle at the widest ring
+constexpr int FL_RMAX = 8, FL_SW = RING_W + 2 * FL_RMAX, FL_SH = RING_H + 2 * FL_RMAX;      // the staged rectangle at the widest ring
 constexpr int FL_HASH = 256, FL_PROBES = 8;      // rows per block in LDS; a thread that finds no slot in FL_PROBES steps goes to memory
 constexpr int FL_STAT = 7;                       // n, lo r g b, hi r g b per table row
-constexpr int FL_NOTEXT = -2, FL_NOROW = -1;     // staged values below the table rows: not text (or off the page); text of no table row
 
 static inline bool flat_geometry(int h, int w, int max_regions) {
     return h >= 1 && w >= 1 && (int64_t)h * w <= (1ll << 31) - 2 && max_regions >= 1;
@@ -46,21 +30,9 @@ static inline bool flat_geometry(int h, int w, int max_regions) {
 // ws: u64 sum[max_regions][3] | int stat[max_regions][FL_STAT]
 static inline size_t flat_ws_bytes(int max_regions) { return (size_t)max_regions * (3 * sizeof(u64) + FL_STAT * sizeof(int)); }
 
-__device__ __forceinline__ int clamp_count(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// the table row whose label is lab, FL_NOROW without one (the table ascends in label)
-__device__ __forceinline__ int find_row(const int* __restrict__ table, int R, int lab) {
-    int lo = 0, hi = R;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (table[(int64_t)mid * 6] < lab) lo = mid + 1; else hi = mid;
-    }
-    return (lo < R && table[(int64_t)lo * 6] == lab) ? lo : FL_NOROW;
-}
-
 // ---- 1. init ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FL_THREADS) void flat_init_kernel(int max_regions, u64* __restrict__ sum, int* __restrict__ stat) {
-    const int r = blockIdx.x * FL_THREADS + threadIdx.x;
+__global__ __launch_bounds__(RING_THREADS) void flat_init_kernel(int max_regions, u64* __restrict__ sum, int* __restrict__ stat) {
+    const int r = blockIdx.x * RING_THREADS + threadIdx.x;
     if (r >= max_regions) return;
     sum[(int64_t)r * 3] = sum[(int64_t)r * 3 + 1] = sum[(int64_t)r * 3 + 2] = 0;
     int* s = stat + (int64_t)r * FL_STAT;
@@ -85,7 +57,7 @@ __device__ __forceinline__ void stats_to_memory(int row, int n, int lo0, int lo1
     atomicMax(s + 4, hi0); atomicMax(s + 5, hi1); atomicMax(s + 6, hi2);
     atomicAdd(sum + (int64_t)row * 3, (u64)s0); atomicAdd(sum + (int64_t)row * 3 + 1, (u64)s1); atomicAdd(sum + (int64_t)row * 3 + 2, (u64)s2);
 }
-// a block's sums stay below FL_W * FL_H * 255 < 2^31
+// a block's sums stay below RING_W * RING_H * 255 < 2^31
 __device__ __forceinline__ void acc_flush(const RingAcc& a, int* hkey, int* hn, int (*hlo)[FL_HASH], int (*hhi)[FL_HASH], int (*hsum)[FL_HASH],
                                           u64* sum, int* stat) {
     if (a.n == 0) return;
@@ -105,90 +77,43 @@ __device__ __forceinline__ void acc_flush(const RingAcc& a, int* hkey, int* hn, 
     stats_to_memory(a.row, a.n, a.lo[0], a.lo[1], a.lo[2], a.hi[0], a.hi[1], a.hi[2], a.sum[0], a.sum[1], a.sum[2], sum, stat);
 }
 
-__global__ __launch_bounds__(FL_THREADS) void flat_ring_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text,
-                                                               const int* __restrict__ labels, int h, int w, int nbx,
-                                                               const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
-                                                               int ring, u64* sum, int* stat) {
-    __shared__ int idx[FL_SH * FL_SW];               // rows of sw = FL_W + 2 ring entries: table row, FL_NOROW or FL_NOTEXT
-    __shared__ u64 hrow[FL_SH];                      // bit c: a pixel with a table row in staged columns c .. c + 2 ring of this staged row
-    __shared__ u64 vnear[FL_H];                      // bit c: ... within `ring` of the block's pixel (row, c)
+__global__ __launch_bounds__(RING_THREADS) void flat_ring_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text,
+                                                                 const int* __restrict__ labels, int h, int w, int nbx,
+                                                                 const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
+                                                                 int ring, u64* sum, int* stat) {
+    __shared__ int idx[FL_SH * FL_SW];               // region_ring.h, stage_rows
+    __shared__ u64 hrow[FL_SH], vnear[RING_H];       // region_ring.h, near_bits
     __shared__ int hkey[FL_HASH], hn[FL_HASH], hlo[3][FL_HASH], hhi[3][FL_HASH], hsum[3][FL_HASH];
     const int tid = threadIdx.x;
-    const int x0 = (blockIdx.x % nbx) * FL_W, y0 = (blockIdx.x / nbx) * FL_H;
+    const int x0 = (blockIdx.x % nbx) * RING_W, y0 = (blockIdx.x / nbx) * RING_H;
     const int R = clamp_count(n_regions[1], max_regions);
-    const int sw = FL_W + 2 * ring, sh = FL_H + 2 * ring, span = 2 * ring;
+    const int sw = RING_W + 2 * ring, sh = RING_H + 2 * ring, span = 2 * ring;
     {
-        hkey[tid] = -1; hn[tid] = 0;                 // FL_HASH == FL_THREADS
+        hkey[tid] = -1; hn[tid] = 0;                 // FL_HASH == RING_THREADS
 #pragma unroll
         for (int c = 0; c < 3; ++c) { hlo[c][tid] = 255; hhi[c][tid] = 0; hsum[c][tid] = 0; }
     }
-    for (int j = tid; j < sh * sw; j += FL_THREADS) {
-        const int sr = j / sw, sc = j - sr * sw;
-        const int y = y0 - ring + sr, x = x0 - ring + sc;
-        int v = FL_NOTEXT;
-        if (y >= 0 && y < h && x >= 0 && x < w) {
-            const int64_t p = (int64_t)y * w + x;
-            if (text[p] != 0) v = find_row(table, R, labels[p]);
-        }
-        idx[j] = v;
-    }
-    __syncthreads();
-    if (tid < sh) {                                  // one staged row per thread: its "has a row" bits, dilated to the right by 2 ring
-        u64 lo = 0, hi = 0;
-        const int* s = idx + tid * sw;
-        for (int c = 0; c < sw; ++c) {
-            const u64 b = s[c] >= 0 ? 1ull : 0ull;
-            if (c < 64) lo |= b << c; else hi |= b << (c - 64);
-        }
-        u64 acc = lo;
-        for (int k = 1; k <= span; ++k) acc |= (lo >> k) | (hi << (64 - k));
-        hrow[tid] = acc;
-    }
-    __syncthreads();
-    if (tid < FL_H) {
-        u64 acc = 0;
-        for (int k = 0; k <= span; ++k) acc |= hrow[tid + k];
-        vnear[tid] = acc;
-    }
-    __syncthreads();
+    stage_rows(idx, sw, sh, x0, y0, ring, text, labels, h, w, table, R, tid);
+    near_bits(idx, sw, sh, span, hrow, vnear, tid);
     RingAcc a;
     acc_reset(a, -1);
     const int c = tid & 63, x = x0 + c;
     if (x < w) {
-        for (int k = 0, r = tid >> 6; k < FL_PER; ++k, r += 4) {
-            const int y = y0 + r;
-            if (y >= h || !((vnear[r] >> c) & 1ull) || idx[(r + ring) * sw + c + ring] != FL_NOTEXT) continue;
+        for (int k = 0, r = tid >> 6; k < RING_PER; ++k, r += 4) {
+            const int y = y0 + r;                    // no page bytes are staged: a pixel is text when its own entry says so
+            if (y >= h || !((vnear[r] >> c) & 1ull) || idx[(r + ring) * sw + c + ring] != NOTEXT) continue;
             const uint8_t* px = page + ((int64_t)y * w + x) * 3;
             const int v0 = px[0], v1 = px[1], v2 = px[2];
-            int cur = -1;                            // the rows of the window in ascending order, two per walk
-            for (;;) {
-                int m1 = INT_MAX, m2 = INT_MAX;
-                for (int dy = 0; dy <= span; ++dy) {
-                    const int* s = idx + (r + dy) * sw + c;
-                    for (int dx = 0; dx <= span; ++dx) {
-                        const int v = s[dx];
-                        if (v > cur && v != m1) {
-                            if (v < m1) { m2 = m1; m1 = v; }
-                            else if (v < m2) m2 = v;
-                        }
-                    }
+            for_rows_in_window(idx, sw, r, c, span, [&](int row) {
+                if (row != a.row) {
+                    acc_flush(a, hkey, hn, hlo, hhi, hsum, sum, stat);
+                    acc_reset(a, row);
                 }
-                if (m1 == INT_MAX) break;
-                for (int t = 0; t < 2; ++t) {
-                    const int row = t == 0 ? m1 : m2;
-                    if (row == INT_MAX) break;
-                    if (row != a.row) {
-                        acc_flush(a, hkey, hn, hlo, hhi, hsum, sum, stat);
-                        acc_reset(a, row);
-                    }
-                    ++a.n;
-                    a.lo[0] = v0 < a.lo[0] ? v0 : a.lo[0]; a.lo[1] = v1 < a.lo[1] ? v1 : a.lo[1]; a.lo[2] = v2 < a.lo[2] ? v2 : a.lo[2];
-                    a.hi[0] = v0 > a.hi[0] ? v0 : a.hi[0]; a.hi[1] = v1 > a.hi[1] ? v1 : a.hi[1]; a.hi[2] = v2 > a.hi[2] ? v2 : a.hi[2];
-                    a.sum[0] += v0; a.sum[1] += v1; a.sum[2] += v2;
-                }
-                if (m2 == INT_MAX) break;
-                cur = m2;
-            }
+                ++a.n;
+                a.lo[0] = v0 < a.lo[0] ? v0 : a.lo[0]; a.lo[1] = v1 < a.lo[1] ? v1 : a.lo[1]; a.lo[2] = v2 < a.lo[2] ? v2 : a.lo[2];
+                a.hi[0] = v0 > a.hi[0] ? v0 : a.hi[0]; a.hi[1] = v1 > a.hi[1] ? v1 : a.hi[1]; a.hi[2] = v2 > a.hi[2] ? v2 : a.hi[2];
+                a.sum[0] += v0; a.sum[1] += v1; a.sum[2] += v2;
+            });
         }
     }
     acc_flush(a, hkey, hn, hlo, hhi, hsum, sum, stat);
@@ -199,9 +124,9 @@ __global__ __launch_bounds__(FL_THREADS) void flat_ring_kernel(const uint8_t* __
 }
 
 // ---- 3. decide -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(FL_THREADS) void flat_decide_kernel(const int* __restrict__ n_regions, int max_regions, int tol,
-                                                                 const u64* __restrict__ sum, const int* __restrict__ stat, int* __restrict__ flat) {
-    const int r = blockIdx.x * FL_THREADS + threadIdx.x;
+__global__ __launch_bounds__(RING_THREADS) void flat_decide_kernel(const int* __restrict__ n_regions, int max_regions, int tol,
+                                                                   const u64* __restrict__ sum, const int* __restrict__ stat, int* __restrict__ flat) {
+    const int r = blockIdx.x * RING_THREADS + threadIdx.x;
     if (r >= clamp_count(n_regions[1], max_regions)) return;
     const int* s = stat + (int64_t)r * FL_STAT;
     const int n = s[0];
@@ -214,15 +139,15 @@ __global__ __launch_bounds__(FL_THREADS) void flat_decide_kernel(const int* __re
 
 // ---- 4. apply ------------------------------------------------------------------------------------------------------------------
 // thread tid owns pixels 4 (tid & 15) .. + 3 of rows (tid >> 4) and (tid >> 4) + 16 of the rectangle
-__global__ __launch_bounds__(FL_THREADS) void flat_apply_kernel(const uint8_t* __restrict__ page, uint8_t* text, const int* __restrict__ labels,
-                                                                const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
-                                                                const int* __restrict__ flat, PageGrid g, int nbx, int nby,
-                                                                uint8_t* __restrict__ painted, uint8_t* __restrict__ mask, int* __restrict__ core_count) {
-    __shared__ int wave_count[FL_THREADS / 64];
+__global__ __launch_bounds__(RING_THREADS) void flat_apply_kernel(const uint8_t* __restrict__ page, uint8_t* text, const int* __restrict__ labels,
+                                                                  const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
+                                                                  const int* __restrict__ flat, PageGrid g, int nbx, int nby,
+                                                                  uint8_t* __restrict__ painted, uint8_t* __restrict__ mask, int* __restrict__ core_count) {
+    __shared__ int wave_count[RING_THREADS / 64];
     const int tid = threadIdx.x;
     const int t = blockIdx.x / (nbx * nby), sub = blockIdx.x % (nbx * nby);
     const int ci = t / g.tx, cj = t % g.tx;
-    const int64_t y0 = (int64_t)ci * g.s + (sub / nbx) * FL_H, x0 = (int64_t)cj * g.s + (sub % nbx) * FL_W;
+    const int64_t y0 = (int64_t)ci * g.s + (sub / nbx) * RING_H, x0 = (int64_t)cj * g.s + (sub % nbx) * RING_W;
     const int64_t yend = (int64_t)(ci + 1) * g.s < g.h ? (int64_t)(ci + 1) * g.s : g.h, xend = (int64_t)(cj + 1) * g.s < g.w ? (int64_t)(cj + 1) * g.s : g.w;
     if (y0 >= yend || x0 >= xend) return;               // the whole block
     const int R = clamp_count(n_regions[1], max_regions);
@@ -230,7 +155,7 @@ __global__ __launch_bounds__(FL_THREADS) void flat_apply_kernel(const uint8_t* _
     int cnt = 0;
     if (xa < xend) {
         const int npx = xend - xa < 4 ? (int)(xend - xa) : 4;
-        for (int row = tid >> 4; row < FL_H && y0 + row < yend; row += FL_THREADS / 16) {
+        for (int row = tid >> 4; row < RING_H && y0 + row < yend; row += RING_THREADS / 16) {
             const int64_t p = (y0 + row) * g.w + xa;
             uint8_t b[12], t4[4], m4[4];
             if (npx == 4) {
@@ -244,7 +169,7 @@ __global__ __launch_bounds__(FL_THREADS) void flat_apply_kernel(const uint8_t* _
                     b[3 * k] = page[q * 3]; b[3 * k + 1] = page[q * 3 + 1]; b[3 * k + 2] = page[q * 3 + 2];
                 }
             }
-            int last_lab = 0, last_row = FL_NOROW;
+            int last_lab = 0, last_row = NOROW;
             bool last_flat = false;
 #pragma unroll
             for (int k = 0; k < 4; ++k) {
@@ -288,7 +213,7 @@ __global__ __launch_bounds__(FL_THREADS) void flat_apply_kernel(const uint8_t* _
     __syncthreads();
     if (tid == 0) {
         int total = 0;
-        for (int k = 0; k < FL_THREADS / 64; ++k) total += wave_count[k];
+        for (int k = 0; k < RING_THREADS / 64; ++k) total += wave_count[k];
         if (total > 0) atomicAdd(core_count + t, total);
     }
 }
@@ -313,28 +238,20 @@ extern "C" int tsii_flat_regions(const uint8_t* page, uint8_t* text, const int* 
     TSII_REQUIRE(core_count == nullptr || grid_ok(h, w, tile, halo), "flat_regions: bad geometry h %d w %d tile %d halo %d", h, w, tile, halo);
     TSII_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 7u) == 0, "flat_regions: ws must be 8-byte aligned");
     TSII_REQUIRE(painted != page, "flat_regions: painted must not be the page");
-    PageGrid g;
-    if (core_count != nullptr) g = make_grid(h, w, tile, halo);
-    else {                                              // without counts: cores of 2^20 pixels a side, no tile behind them
-        g.h = h; g.w = w; g.tile = g.s = 1 << 20; g.halo = 0;
-        g.ty = (int)cdiv64(h, g.s); g.tx = (int)cdiv64(w, g.s);
-    }
-    const int nbx = cdiv(g.s < w ? g.s : w, FL_W), nby = cdiv(g.s < h ? g.s : h, FL_H);
-    const int64_t napply = (int64_t)g.ty * g.tx * nbx * nby;
-    const int rbx = cdiv(w, FL_W);
-    const int64_t nring = (int64_t)rbx * cdiv(h, FL_H);
-    TSII_REQUIRE(napply < (1ll << 31) && nring < (1ll << 31), "flat_regions: bad geometry h %d w %d tile %d halo %d (too many blocks)", h, w, tile, halo);
+    const ApplyGrid a = make_apply_grid(h, w, tile, halo, core_count, RING_W, RING_H);
+    const int rbx = cdiv(w, RING_W);
+    const int64_t nring = (int64_t)rbx * cdiv(h, RING_H);
+    TSII_REQUIRE(a.napply < (1ll << 31) && nring < (1ll << 31), "flat_regions: bad geometry h %d w %d tile %d halo %d (too many blocks)", h, w, tile, halo);
     hipStream_t st = (hipStream_t)stream;
-    if (core_count != nullptr && hipMemsetAsync(core_count, 0, sizeof(int) * (size_t)g.ty * g.tx, st) != hipSuccess)
-        return check_launch("flat_regions (memset)");
+    if (!clear_core_count(core_count, a.g, st)) return check_launch("flat_regions (memset)");
     u64* sum = static_cast<u64*>(ws);
     int* stat = reinterpret_cast<int*>(sum + 3 * (size_t)max_regions);
-    const unsigned row_blocks = flat_grid(max_regions, FL_THREADS);
-    hipLaunchKernelGGL(flat_init_kernel, dim3(row_blocks), dim3(FL_THREADS), 0, st, max_regions, sum, stat);
-    hipLaunchKernelGGL(flat_ring_kernel, dim3((unsigned)nring), dim3(FL_THREADS), 0, st, page, text, labels, h, w, rbx, table, n_regions, max_regions,
+    const unsigned row_blocks = flat_grid(max_regions, RING_THREADS);
+    hipLaunchKernelGGL(flat_init_kernel, dim3(row_blocks), dim3(RING_THREADS), 0, st, max_regions, sum, stat);
+    hipLaunchKernelGGL(flat_ring_kernel, dim3((unsigned)nring), dim3(RING_THREADS), 0, st, page, text, labels, h, w, rbx, table, n_regions, max_regions,
                        ring, sum, stat);
-    hipLaunchKernelGGL(flat_decide_kernel, dim3(row_blocks), dim3(FL_THREADS), 0, st, n_regions, max_regions, tol, sum, stat, flat);
-    hipLaunchKernelGGL(flat_apply_kernel, dim3((unsigned)napply), dim3(FL_THREADS), 0, st, page, text, labels, table, n_regions, max_regions, flat,
-                       g, nbx, nby, painted, mask, core_count);
+    hipLaunchKernelGGL(flat_decide_kernel, dim3(row_blocks), dim3(RING_THREADS), 0, st, n_regions, max_regions, tol, sum, stat, flat);
+    hipLaunchKernelGGL(flat_apply_kernel, dim3((unsigned)a.napply), dim3(RING_THREADS), 0, st, page, text, labels, table, n_regions, max_regions, flat,
+                       a.g, a.nbx, a.nby, painted, mask, core_count);
     return check_launch("flat_regions");
 }

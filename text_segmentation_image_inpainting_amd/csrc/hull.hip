@@ -17,17 +17,12 @@
 //   6. finish:   one pass over the plane: bytes to 0 / 1, text pixels per tile core.
 // No grid-wide barrier, no waiting on another block: each step is its own launch.  Everything read from the table or n_regions is
 // clamped before use: a table that does not belong to the labels gives wrong bytes, never an access outside the buffers.
+#include "emu_atomics.h"
 #include "page_grid.h"
 
 #include <limits.h>
 
 namespace tsii {
-
-#ifdef TSII_HIP_EMU
-// the test emulator runs one thread at a time and supplies atomicAdd only
-static inline int atomicMin(int* p, int v) { const int o = *p; if (v < o) *p = v; return o; }
-static inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v; return o; }
-#endif
 
 constexpr int HL_THREADS = 256;
 constexpr int HL_W = 64, HL_H = 32;              // rectangle of the finish kernel: a wave reads 64 consecutive bytes of a row
@@ -339,18 +334,10 @@ extern "C" int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w,
                  h, w, max_regions);
     TSII_REQUIRE(core_count == nullptr || grid_ok(h, w, tile, halo), "region_hulls: bad geometry h %d w %d tile %d halo %d", h, w, tile, halo);
     TSII_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3u) == 0, "region_hulls: ws must be 4-byte aligned");
-    PageGrid g;
-    if (core_count != nullptr) g = make_grid(h, w, tile, halo);
-    else {                                              // without counts: cores of 2^20 pixels a side, no tile behind them
-        g.h = h; g.w = w; g.tile = g.s = 1 << 20; g.halo = 0;
-        g.ty = (int)cdiv64(h, g.s); g.tx = (int)cdiv64(w, g.s);
-    }
-    const int nbx = cdiv(g.s < w ? g.s : w, HL_W), nby = cdiv(g.s < h ? g.s : h, HL_H);
-    const int64_t nfinish = (int64_t)g.ty * g.tx * nbx * nby;
-    TSII_REQUIRE(nfinish < (1ll << 31), "region_hulls: bad geometry h %d w %d tile %d halo %d (too many tile cores)", h, w, tile, halo);
+    const ApplyGrid a = make_apply_grid(h, w, tile, halo, core_count, HL_W, HL_H);
+    TSII_REQUIRE(a.napply < (1ll << 31), "region_hulls: bad geometry h %d w %d tile %d halo %d (too many tile cores)", h, w, tile, halo);
     hipStream_t st = (hipStream_t)stream;
-    if (core_count != nullptr && hipMemsetAsync(core_count, 0, sizeof(int) * (size_t)g.ty * g.tx, st) != hipSuccess)
-        return check_launch("region_hulls (memset)");
+    if (!clear_core_count(core_count, a.g, st)) return check_launch("region_hulls (memset)");
     const HullWs s = hull_ws(ws, max_regions, npairs);
     const unsigned pair_blocks = flat_grid(npairs, HL_THREADS);
     hipLaunchKernelGGL(hull_offsets_kernel, dim3(1), dim3(HL_THREADS), 0, st, table, n_regions, max_regions, h, npairs, s.hdr, s.roff, s.rht, hull_area);
@@ -359,6 +346,6 @@ extern "C" int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w,
                        s.rht, s.ext);
     hipLaunchKernelGGL(hull_vertices_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, w, s.hdr, s.roff, s.rht, s.ext, s.vflag);
     hipLaunchKernelGGL(hull_fill_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, text, h, w, table, s.hdr, s.roff, s.rht, s.ext, s.vflag, hull_area);
-    hipLaunchKernelGGL(hull_finish_kernel, dim3((unsigned)nfinish), dim3(HL_THREADS), 0, st, text, g, nbx, nby, core_count);
+    hipLaunchKernelGGL(hull_finish_kernel, dim3((unsigned)a.napply), dim3(HL_THREADS), 0, st, text, a.g, a.nbx, a.nby, core_count);
     return check_launch("region_hulls");
 }

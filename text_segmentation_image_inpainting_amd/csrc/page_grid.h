@@ -18,4 +18,28 @@ static inline bool grid_ok(int h, int w, int tile, int halo) {
            (int64_t)h * w < (1ll << 31) - 4 && (int64_t)cdiv(h, tile - 2 * halo) * cdiv(w, tile - 2 * halo) * tile * (tile / 4) < (1ll << 31);
 }
 
+// What the kernels that walk the tile cores in rectangles of bw x bh pixels, one block each, launch on (the finish kernel of hull.hip,
+// the apply kernels of region_ring.h): nbx x nby rectangles per core, napply blocks in all.  With counts the cores are the grid's;
+// without, cores of 2^20 pixels a side with no tile behind them.
+struct ApplyGrid {
+    PageGrid g;
+    int nbx, nby;
+    int64_t napply;
+};
+static inline ApplyGrid make_apply_grid(int h, int w, int tile, int halo, const int* core_count, int bw, int bh) {
+    ApplyGrid a;
+    if (core_count != nullptr) a.g = make_grid(h, w, tile, halo);
+    else {
+        a.g.h = h; a.g.w = w; a.g.tile = a.g.s = 1 << 20; a.g.halo = 0;
+        a.g.ty = (int)cdiv64(h, a.g.s); a.g.tx = (int)cdiv64(w, a.g.s);
+    }
+    a.nbx = cdiv(a.g.s < w ? a.g.s : w, bw); a.nby = cdiv(a.g.s < h ? a.g.s : h, bh);
+    a.napply = (int64_t)a.g.ty * a.g.tx * a.nbx * a.nby;
+    return a;
+}
+// the counts of all cores to 0 (nothing to do without counts); false: the memset did not start
+static inline bool clear_core_count(int* core_count, const PageGrid& g, hipStream_t st) {
+    return core_count == nullptr || hipMemsetAsync(core_count, 0, sizeof(int) * (size_t)g.ty * g.tx, st) == hipSuccess;
+}
+
 }  // namespace tsii

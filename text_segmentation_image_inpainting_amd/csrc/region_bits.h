@@ -1,18 +1,12 @@
 // What regions.hip (K10) and blocks.hip (K15) share: the 64 x 32 rectangle a block of 256 threads owns, its rows as 64-bit words, the
 // run helpers on those words and the block scan of the table kernels.  Device helpers only: every kernel stays in its own file.
 #pragma once
+#include "emu_atomics.h"
 #include "page_grid.h"
 
 #include <limits.h>
 
 namespace tsii {
-
-#ifdef TSII_HIP_EMU
-// the test emulator runs one thread at a time and supplies atomicAdd only
-static inline int atomicMin(int* p, int v) { const int o = *p; if (v < o) *p = v; return o; }
-static inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v; return o; }
-static inline int atomicCAS(int* p, int expect, int v) { const int o = *p; if (o == expect) *p = v; return o; }
-#endif
 
 constexpr int RG_W = 64, RG_H = 32, RG_PIX = RG_W * RG_H, RG_THREADS = 256, RG_PER = RG_PIX / RG_THREADS;
 constexpr int RG_SCAN = 8;                       // segment counts per thread of the scan kernels

@@ -6,68 +6,43 @@
 //
 //   classify 1. init:   the statistics of all max_regions table rows (nothing in ws has to be cleared by the caller);
 //            2. stage:  x = byte / 255 and valid = (text == 0) over the whole page, 4 pixels and four 16-byte stores per thread;
-//            3. ring:   K13's ring kernel (csrc/flat.hip) with another statistic.  A block owns SM_W x SM_H page pixels and stages, for
-//                       them and an apron of `ring` pixels, the table row of every text pixel, and, for them and an apron of ONE pixel,
-//                       the page bytes of the non-text pixels: the local step d of a pixel needs its 4-neighbours only, so what the
-//                       block reads lies within ring + 1 of its rectangle.  d is computed once per pixel from LDS; the window walk, the
-//                       LDS table of the rows a block meets and the one set of integer atomics per (block, row) -- atomicAdd on n,
-//                       atomicMax on the three steps, 32 bits all -- are K13's;
+//            3. ring:   the ring walk of region_ring.h with another statistic than K13's.  A block owns RING_W x RING_H page pixels and
+//                       stages, for them and an apron of `ring` pixels, the table row of every text pixel (stage_rows), and, for them and
+//                       an apron of ONE pixel, the page bytes of the non-text pixels (stage_pixels): the local step d of a pixel needs
+//                       its 4-neighbours only, so what the block reads lies within ring + 1 of its rectangle.  d is computed once per
+//                       pixel from LDS and goes to every row of the pixel's window (for_rows_in_window); rows meet per block in an LDS
+//                       hash table and leave it as one set of integer atomics per (block, row) -- atomicAdd on n, atomicMax on the
+//                       three steps, 32 bits all;
 //            4. decide: one thread per table row -> `smooth`;
-//   apply:   K13's apply geometry: a block owns an SM_W x SM_H rectangle of one tile core, a thread 4 consecutive pixels of a row; `filled`
-//            is read on the text pixels of smooth rows only.
+//   apply:   K13's apply kernel (csrc/flat.hip) with another paint: a block owns a RING_W x RING_H rectangle of one tile core, a thread 4
+//            consecutive pixels of a row; `filled` is read on the text pixels of smooth rows only.
 // No grid-wide barrier, no waiting on another block: each step is its own launch.  The count read from n_regions is clamped to max_regions
 // and a row found by the search lies below it: a table that does not belong to the labels gives wrong bytes, never an access outside the
-// buffers.  The boxes of the table are not read.  The ring walk is a copy of K13's and not a shared header: flat.hip stays as it is.
-#include "page_grid.h"
-
-#include <limits.h>
-#include <string.h>
+// buffers.  The boxes of the table are not read.
+#include "region_ring.h"
 
 namespace tsii {
 
-typedef unsigned long long u64;
-
-#ifdef TSII_HIP_EMU
-// the test emulator runs one thread at a time and supplies the 32-bit atomicAdd only
-static inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v; return o; }
-static inline int atomicCAS(int* p, int expect, int v) { const int o = *p; if (o == expect) *p = v; return o; }
-#endif
-
-constexpr int SM_W = 64, SM_H = 32, SM_THREADS = 256, SM_PER = SM_W * SM_H / SM_THREADS;
-constexpr int SM_RMAX = 8, SM_SW = SM_W + 2 * SM_RMAX, SM_SH = SM_H + 2 * SM_RMAX;      // the staged rectangle at the widest ring
-constexpr int SM_PW = SM_W + 2, SM_PH = SM_H + 2;                                        // the staged page bytes: an apron of one pixel
+constexpr int SM_RMAX = 8, SM_SW = RING_W + 2 * SM_RMAX, SM_SH = RING_H + 2 * SM_RMAX;   // the staged rectangle at the widest ring
+constexpr int SM_PW = RING_W + 2, SM_PH = RING_H + 2;                                    // the staged page bytes: an apron of one pixel
 constexpr int SM_HASH = 256, SM_PROBES = 8;      // rows per block in LDS; a thread that finds no slot in SM_PROBES steps goes to memory
 constexpr int SM_STAT = 4;                       // n, step r g b per table row
-constexpr int SM_NOTEXT = -2, SM_NOROW = -1;     // staged values below the table rows: not text (or off the page); text of no table row
-constexpr int SM_NOPIX = -1;                     // staged page bytes: text, or off the page
 
 static inline bool smooth_geometry(int h, int w, int max_regions) {
     return h >= 1 && w >= 1 && (int64_t)h * w * 3 <= (1ll << 31) && max_regions >= 1;
 }
 
-__device__ __forceinline__ int sm_clamp_count(int v, int hi) { return v < 0 ? 0 : (v > hi ? hi : v); }
-
-// the table row whose label is lab, SM_NOROW without one (the table ascends in label)
-__device__ __forceinline__ int sm_find_row(const int* __restrict__ table, int R, int lab) {
-    int lo = 0, hi = R;
-    while (lo < hi) {
-        const int mid = (lo + hi) >> 1;
-        if (table[(int64_t)mid * 6] < lab) lo = mid + 1; else hi = mid;
-    }
-    return (lo < R && table[(int64_t)lo * 6] == lab) ? lo : SM_NOROW;
-}
-
 // ---- 1. init ---------------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SM_THREADS) void smooth_init_kernel(int max_regions, int* __restrict__ stat) {
-    const int64_t i = (int64_t)blockIdx.x * SM_THREADS + threadIdx.x;
+__global__ __launch_bounds__(RING_THREADS) void smooth_init_kernel(int max_regions, int* __restrict__ stat) {
+    const int64_t i = (int64_t)blockIdx.x * RING_THREADS + threadIdx.x;
     if (i < (int64_t)max_regions * SM_STAT) stat[i] = 0;
 }
 
 // ---- 2. the solver's operands --------------------------------------------------------------------------------------------------------
 // thread i owns pixels 4 i .. 4 i + 3 of the page taken as one row of n pixels; vec: every pointer has the alignment of its vector
-__global__ __launch_bounds__(SM_THREADS) void smooth_stage_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text, int64_t n,
-                                                                  int vec, float* __restrict__ x, float* __restrict__ valid) {
-    const int64_t p = ((int64_t)blockIdx.x * SM_THREADS + threadIdx.x) * 4;
+__global__ __launch_bounds__(RING_THREADS) void smooth_stage_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text, int64_t n,
+                                                                    int vec, float* __restrict__ x, float* __restrict__ valid) {
+    const int64_t p = ((int64_t)blockIdx.x * RING_THREADS + threadIdx.x) * 4;
     if (p >= n) return;
     if (vec && p + 4 <= n) {
         uint8_t b[12], t4[4];
@@ -118,109 +93,53 @@ __device__ __forceinline__ void sm_flush(const StepAcc& a, int* hkey, int* hn, i
 
 // |a - b| per byte of two staged pixels, the maximum with d so far
 __device__ __forceinline__ void sm_step(int a, int b, int& d0, int& d1, int& d2) {
-    if (b == SM_NOPIX) return;
-    const int e0 = (a & 255) - (b & 255), e1 = ((a >> 8) & 255) - ((b >> 8) & 255), e2 = ((a >> 16) & 255) - ((b >> 16) & 255);
-    const int f0 = e0 < 0 ? -e0 : e0, f1 = e1 < 0 ? -e1 : e1, f2 = e2 < 0 ? -e2 : e2;
+    if (b == NOPIX) return;
+    int f0, f1, f2;
+    abs_diff3(a, b, f0, f1, f2);
     d0 = f0 > d0 ? f0 : d0; d1 = f1 > d1 ? f1 : d1; d2 = f2 > d2 ? f2 : d2;
 }
 
-__global__ __launch_bounds__(SM_THREADS) void smooth_ring_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text,
-                                                                 const int* __restrict__ labels, int h, int w, int nbx,
-                                                                 const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
-                                                                 int ring, int* stat) {
-    __shared__ int idx[SM_SH * SM_SW];               // rows of sw = SM_W + 2 ring entries: table row, SM_NOROW or SM_NOTEXT
-    __shared__ int pix[SM_PH * SM_PW];               // r | g << 8 | b << 16 of the non-text pixels, SM_NOPIX elsewhere
-    __shared__ u64 hrow[SM_SH];                      // bit c: a pixel with a table row in staged columns c .. c + 2 ring of this staged row
-    __shared__ u64 vnear[SM_H];                      // bit c: ... within `ring` of the block's pixel (row, c)
+__global__ __launch_bounds__(RING_THREADS) void smooth_ring_kernel(const uint8_t* __restrict__ page, const uint8_t* __restrict__ text,
+                                                                   const int* __restrict__ labels, int h, int w, int nbx,
+                                                                   const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
+                                                                   int ring, int* stat) {
+    __shared__ int idx[SM_SH * SM_SW];               // region_ring.h, stage_rows
+    __shared__ int pix[SM_PH * SM_PW];               // region_ring.h, stage_pixels
+    __shared__ u64 hrow[SM_SH], vnear[RING_H];       // region_ring.h, near_bits
     __shared__ int hkey[SM_HASH], hn[SM_HASH], hstep[3][SM_HASH];
     const int tid = threadIdx.x;
-    const int x0 = (blockIdx.x % nbx) * SM_W, y0 = (blockIdx.x / nbx) * SM_H;
-    const int R = sm_clamp_count(n_regions[1], max_regions);
-    const int sw = SM_W + 2 * ring, sh = SM_H + 2 * ring, span = 2 * ring;
+    const int x0 = (blockIdx.x % nbx) * RING_W, y0 = (blockIdx.x / nbx) * RING_H;
+    const int R = clamp_count(n_regions[1], max_regions);
+    const int sw = RING_W + 2 * ring, sh = RING_H + 2 * ring, span = 2 * ring;
     {
-        hkey[tid] = -1; hn[tid] = 0;                 // SM_HASH == SM_THREADS
+        hkey[tid] = -1; hn[tid] = 0;                 // SM_HASH == RING_THREADS
         hstep[0][tid] = hstep[1][tid] = hstep[2][tid] = 0;
     }
-    for (int j = tid; j < sh * sw; j += SM_THREADS) {
-        const int sr = j / sw, sc = j - sr * sw;
-        const int y = y0 - ring + sr, x = x0 - ring + sc;
-        int v = SM_NOTEXT;
-        if (y >= 0 && y < h && x >= 0 && x < w) {
-            const int64_t p = (int64_t)y * w + x;
-            if (text[p] != 0) v = sm_find_row(table, R, labels[p]);
-        }
-        idx[j] = v;
-    }
-    for (int j = tid; j < SM_PH * SM_PW; j += SM_THREADS) {
-        const int sr = j / SM_PW, sc = j - sr * SM_PW;
-        const int y = y0 - 1 + sr, x = x0 - 1 + sc;
-        int v = SM_NOPIX;
-        if (y >= 0 && y < h && x >= 0 && x < w) {
-            const int64_t p = (int64_t)y * w + x;
-            if (text[p] == 0) v = (int)page[p * 3] | ((int)page[p * 3 + 1] << 8) | ((int)page[p * 3 + 2] << 16);
-        }
-        pix[j] = v;
-    }
-    __syncthreads();
-    if (tid < sh) {                                  // one staged row per thread: its "has a row" bits, dilated to the right by 2 ring
-        u64 lo = 0, hi = 0;
-        const int* s = idx + tid * sw;
-        for (int c = 0; c < sw; ++c) {
-            const u64 b = s[c] >= 0 ? 1ull : 0ull;
-            if (c < 64) lo |= b << c; else hi |= b << (c - 64);
-        }
-        u64 acc = lo;
-        for (int k = 1; k <= span; ++k) acc |= (lo >> k) | (hi << (64 - k));
-        hrow[tid] = acc;
-    }
-    __syncthreads();
-    if (tid < SM_H) {
-        u64 acc = 0;
-        for (int k = 0; k <= span; ++k) acc |= hrow[tid + k];
-        vnear[tid] = acc;
-    }
-    __syncthreads();
+    stage_rows(idx, sw, sh, x0, y0, ring, text, labels, h, w, table, R, tid);
+    stage_pixels(pix, SM_PW, SM_PH, x0 - 1, y0 - 1, page, text, h, w, tid);
+    near_bits(idx, sw, sh, span, hrow, vnear, tid);
     StepAcc a;
     sm_reset(a, -1);
     const int c = tid & 63, x = x0 + c;
     if (x < w) {
-        for (int k = 0, r = tid >> 6; k < SM_PER; ++k, r += 4) {
+        for (int k = 0, r = tid >> 6; k < RING_PER; ++k, r += 4) {
             const int y = y0 + r;
             if (y >= h || !((vnear[r] >> c) & 1ull)) continue;
             const int* pc = pix + (r + 1) * SM_PW + c + 1;
             const int me = pc[0];
-            if (me == SM_NOPIX) continue;            // text
+            if (me == NOPIX) continue;               // text
             int d0 = 0, d1 = 0, d2 = 0;              // the local step: against the non-text 4-neighbours on the page
             sm_step(me, pc[-SM_PW], d0, d1, d2); sm_step(me, pc[SM_PW], d0, d1, d2);
             sm_step(me, pc[-1], d0, d1, d2); sm_step(me, pc[1], d0, d1, d2);
-            int cur = -1;                            // the rows of the window in ascending order, two per walk
-            for (;;) {
-                int m1 = INT_MAX, m2 = INT_MAX;
-                for (int dy = 0; dy <= span; ++dy) {
-                    const int* s = idx + (r + dy) * sw + c;
-                    for (int dx = 0; dx <= span; ++dx) {
-                        const int v = s[dx];
-                        if (v > cur && v != m1) {
-                            if (v < m1) { m2 = m1; m1 = v; }
-                            else if (v < m2) m2 = v;
-                        }
-                    }
+            for_rows_in_window(idx, sw, r, c, span, [&](int row) {
+                if (row != a.row) {
+                    sm_flush(a, hkey, hn, hstep, stat);
+                    sm_reset(a, row);
                 }
-                if (m1 == INT_MAX) break;
-                for (int t = 0; t < 2; ++t) {
-                    const int row = t == 0 ? m1 : m2;
-                    if (row == INT_MAX) break;
-                    if (row != a.row) {
-                        sm_flush(a, hkey, hn, hstep, stat);
-                        sm_reset(a, row);
-                    }
-                    ++a.n;
-                    a.step[0] = d0 > a.step[0] ? d0 : a.step[0]; a.step[1] = d1 > a.step[1] ? d1 : a.step[1];
-                    a.step[2] = d2 > a.step[2] ? d2 : a.step[2];
-                }
-                if (m2 == INT_MAX) break;
-                cur = m2;
-            }
+                ++a.n;
+                a.step[0] = d0 > a.step[0] ? d0 : a.step[0]; a.step[1] = d1 > a.step[1] ? d1 : a.step[1];
+                a.step[2] = d2 > a.step[2] ? d2 : a.step[2];
+            });
         }
     }
     sm_flush(a, hkey, hn, hstep, stat);
@@ -229,10 +148,10 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_ring_kernel(const uint8_t* 
 }
 
 // ---- 4. decide -----------------------------------------------------------------------------------------------------------------
-__global__ __launch_bounds__(SM_THREADS) void smooth_decide_kernel(const int* __restrict__ n_regions, int max_regions, int tol,
-                                                                   const int* __restrict__ stat, int* __restrict__ smooth) {
-    const int r = blockIdx.x * SM_THREADS + threadIdx.x;
-    if (r >= sm_clamp_count(n_regions[1], max_regions)) return;
+__global__ __launch_bounds__(RING_THREADS) void smooth_decide_kernel(const int* __restrict__ n_regions, int max_regions, int tol,
+                                                                     const int* __restrict__ stat, int* __restrict__ smooth) {
+    const int r = blockIdx.x * RING_THREADS + threadIdx.x;
+    if (r >= clamp_count(n_regions[1], max_regions)) return;
     const int* s = stat + (int64_t)r * SM_STAT;
     int* f = smooth + (int64_t)r * 5;
     f[0] = (s[0] >= 1 && s[1] <= tol && s[2] <= tol && s[3] <= tol) ? 1 : 0;
@@ -250,24 +169,24 @@ __device__ __forceinline__ uint8_t sm_byte(float v) {
 }
 
 // thread tid owns pixels 4 (tid & 15) .. + 3 of rows (tid >> 4) and (tid >> 4) + 16 of the rectangle
-__global__ __launch_bounds__(SM_THREADS) void smooth_apply_kernel(const uint8_t* __restrict__ page, uint8_t* text, const int* __restrict__ labels,
-                                                                  const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
-                                                                  const int* __restrict__ smooth, const float* __restrict__ filled, PageGrid g,
-                                                                  int nbx, int nby, uint8_t* __restrict__ painted, uint8_t* __restrict__ mask,
-                                                                  int* __restrict__ core_count) {
-    __shared__ int wave_count[SM_THREADS / 64];
+__global__ __launch_bounds__(RING_THREADS) void smooth_apply_kernel(const uint8_t* __restrict__ page, uint8_t* text, const int* __restrict__ labels,
+                                                                    const int* __restrict__ table, const int* __restrict__ n_regions, int max_regions,
+                                                                    const int* __restrict__ smooth, const float* __restrict__ filled, PageGrid g,
+                                                                    int nbx, int nby, uint8_t* __restrict__ painted, uint8_t* __restrict__ mask,
+                                                                    int* __restrict__ core_count) {
+    __shared__ int wave_count[RING_THREADS / 64];
     const int tid = threadIdx.x;
     const int t = blockIdx.x / (nbx * nby), sub = blockIdx.x % (nbx * nby);
     const int ci = t / g.tx, cj = t % g.tx;
-    const int64_t y0 = (int64_t)ci * g.s + (sub / nbx) * SM_H, x0 = (int64_t)cj * g.s + (sub % nbx) * SM_W;
+    const int64_t y0 = (int64_t)ci * g.s + (sub / nbx) * RING_H, x0 = (int64_t)cj * g.s + (sub % nbx) * RING_W;
     const int64_t yend = (int64_t)(ci + 1) * g.s < g.h ? (int64_t)(ci + 1) * g.s : g.h, xend = (int64_t)(cj + 1) * g.s < g.w ? (int64_t)(cj + 1) * g.s : g.w;
     if (y0 >= yend || x0 >= xend) return;               // the whole block
-    const int R = sm_clamp_count(n_regions[1], max_regions);
+    const int R = clamp_count(n_regions[1], max_regions);
     const int64_t xa = x0 + 4 * (tid & 15);
     int cnt = 0;
     if (xa < xend) {
         const int npx = xend - xa < 4 ? (int)(xend - xa) : 4;
-        for (int row = tid >> 4; row < SM_H && y0 + row < yend; row += SM_THREADS / 16) {
+        for (int row = tid >> 4; row < RING_H && y0 + row < yend; row += RING_THREADS / 16) {
             const int64_t p = (y0 + row) * g.w + xa;
             uint8_t b[12], t4[4], m4[4];
             if (npx == 4) {
@@ -290,7 +209,7 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_apply_kernel(const uint8_t*
                 const int lab = labels[p + k];
                 if (lab != last_lab) {
                     last_lab = lab;
-                    const int found = sm_find_row(table, R, lab);
+                    const int found = find_row(table, R, lab);
                     last_smooth = found >= 0 && smooth[(int64_t)found * 5] != 0;
                 }
                 if (last_smooth) {
@@ -325,7 +244,7 @@ __global__ __launch_bounds__(SM_THREADS) void smooth_apply_kernel(const uint8_t*
     __syncthreads();
     if (tid == 0) {
         int total = 0;
-        for (int k = 0; k < SM_THREADS / 64; ++k) total += wave_count[k];
+        for (int k = 0; k < RING_THREADS / 64; ++k) total += wave_count[k];
         if (total > 0) atomicAdd(core_count + t, total);
     }
 }
@@ -348,17 +267,17 @@ extern "C" int tsii_smooth_regions_classify(const uint8_t* page, const uint8_t* 
     TSII_REQUIRE(ring >= 1 && ring <= SM_RMAX, "smooth_regions_classify: ring %d (1..%d)", ring, SM_RMAX);
     TSII_REQUIRE(tol >= 0 && tol <= 255, "smooth_regions_classify: tol %d (0..255)", tol);
     TSII_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3u) == 0, "smooth_regions_classify: ws must be 4-byte aligned");
-    const int rbx = cdiv(w, SM_W);
-    const int64_t nring = (int64_t)rbx * cdiv(h, SM_H), n = (int64_t)h * w;
+    const int rbx = cdiv(w, RING_W);
+    const int64_t nring = (int64_t)rbx * cdiv(h, RING_H), n = (int64_t)h * w;
     TSII_REQUIRE(nring < (1ll << 31), "smooth_regions_classify: page of %d x %d pixels (too many blocks)", h, w);
     hipStream_t st = (hipStream_t)stream;
     int* stat = static_cast<int*>(ws);
     const int vec = aligned16(x) && aligned16(valid) && (reinterpret_cast<uintptr_t>(page) & 3u) == 0 && (reinterpret_cast<uintptr_t>(text) & 3u) == 0;
-    hipLaunchKernelGGL(smooth_init_kernel, dim3(flat_grid((int64_t)max_regions * SM_STAT, SM_THREADS)), dim3(SM_THREADS), 0, st, max_regions, stat);
-    hipLaunchKernelGGL(smooth_stage_kernel, dim3(flat_grid(cdiv64(n, 4), SM_THREADS)), dim3(SM_THREADS), 0, st, page, text, n, vec, x, valid);
-    hipLaunchKernelGGL(smooth_ring_kernel, dim3((unsigned)nring), dim3(SM_THREADS), 0, st, page, text, labels, h, w, rbx, table, n_regions, max_regions,
+    hipLaunchKernelGGL(smooth_init_kernel, dim3(flat_grid((int64_t)max_regions * SM_STAT, RING_THREADS)), dim3(RING_THREADS), 0, st, max_regions, stat);
+    hipLaunchKernelGGL(smooth_stage_kernel, dim3(flat_grid(cdiv64(n, 4), RING_THREADS)), dim3(RING_THREADS), 0, st, page, text, n, vec, x, valid);
+    hipLaunchKernelGGL(smooth_ring_kernel, dim3((unsigned)nring), dim3(RING_THREADS), 0, st, page, text, labels, h, w, rbx, table, n_regions, max_regions,
                        ring, stat);
-    hipLaunchKernelGGL(smooth_decide_kernel, dim3(flat_grid(max_regions, SM_THREADS)), dim3(SM_THREADS), 0, st, n_regions, max_regions, tol, stat, smooth);
+    hipLaunchKernelGGL(smooth_decide_kernel, dim3(flat_grid(max_regions, RING_THREADS)), dim3(RING_THREADS), 0, st, n_regions, max_regions, tol, stat, smooth);
     return check_launch("smooth_regions_classify");
 }
 
@@ -370,19 +289,11 @@ extern "C" int tsii_smooth_regions_apply(const uint8_t* page, uint8_t* text, con
                  "smooth_regions_apply: page of %d x %d pixels, max_regions %d (h, w >= 1, h * w * 3 <= 2^31, max_regions >= 1)", h, w, max_regions);
     TSII_REQUIRE(core_count == nullptr || grid_ok(h, w, tile, halo), "smooth_regions_apply: bad geometry h %d w %d tile %d halo %d", h, w, tile, halo);
     TSII_REQUIRE(painted != page, "smooth_regions_apply: painted must not be the page");
-    PageGrid g;
-    if (core_count != nullptr) g = make_grid(h, w, tile, halo);
-    else {                                              // without counts: cores of 2^20 pixels a side, no tile behind them
-        g.h = h; g.w = w; g.tile = g.s = 1 << 20; g.halo = 0;
-        g.ty = (int)cdiv64(h, g.s); g.tx = (int)cdiv64(w, g.s);
-    }
-    const int nbx = cdiv(g.s < w ? g.s : w, SM_W), nby = cdiv(g.s < h ? g.s : h, SM_H);
-    const int64_t napply = (int64_t)g.ty * g.tx * nbx * nby;
-    TSII_REQUIRE(napply < (1ll << 31), "smooth_regions_apply: bad geometry h %d w %d tile %d halo %d (too many blocks)", h, w, tile, halo);
+    const ApplyGrid a = make_apply_grid(h, w, tile, halo, core_count, RING_W, RING_H);
+    TSII_REQUIRE(a.napply < (1ll << 31), "smooth_regions_apply: bad geometry h %d w %d tile %d halo %d (too many blocks)", h, w, tile, halo);
     hipStream_t st = (hipStream_t)stream;
-    if (core_count != nullptr && hipMemsetAsync(core_count, 0, sizeof(int) * (size_t)g.ty * g.tx, st) != hipSuccess)
-        return check_launch("smooth_regions_apply (memset)");
-    hipLaunchKernelGGL(smooth_apply_kernel, dim3((unsigned)napply), dim3(SM_THREADS), 0, st, page, text, labels, table, n_regions, max_regions, smooth,
-                       filled, g, nbx, nby, painted, mask, core_count);
+    if (!clear_core_count(core_count, a.g, st)) return check_launch("smooth_regions_apply (memset)");
+    hipLaunchKernelGGL(smooth_apply_kernel, dim3((unsigned)a.napply), dim3(RING_THREADS), 0, st, page, text, labels, table, n_regions, max_regions, smooth,
+                       filled, a.g, a.nbx, a.nby, painted, mask, core_count);
     return check_launch("smooth_regions_apply");
 }

@@ -39,9 +39,9 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import (_flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args,
-                      check_flat_args, check_region_args, check_smooth_args, check_tone_args, unpack_blocks, unpack_flat, unpack_hull_area,
-                      unpack_regions, unpack_smooth, unpack_tone)
+from .regions import (RouteLayout, _flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args,
+                      check_flat_args, check_region_args, check_smooth_args, check_tone_args, unpack_blocks, unpack_hull_area, unpack_regions,
+                      unpack_routes)
 
 
 class TileGrid(NamedTuple):
@@ -438,14 +438,14 @@ class TextEraser:
         self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=self._tail())
         return packed
 
+    def _layout(self, nt=0):
+        """where the rows of the enabled ones of the flat, smooth and tone stages ride behind the table of the labelling they work on
+        (``nt``: the core counts in front of it); tools/erase_bench.py unpacks its read-back with it"""
+        return RouteLayout(nt, self.max_regions, self.flat is not None, self.smooth is not None, self.tone is not None)
+
     def _tail(self):
         """the words behind the table that the stage behind it writes"""
-        return self.max_regions if self.hull else self._route_tail()
-
-    def _route_tail(self):
-        """the words behind the table of the labelling the flat, smooth and tone stages work on: 5 per row for flat, 5 for smooth, 6 for
-        tone, in that order"""
-        return self.max_regions * (5 * ((self.flat is not None) + (self.smooth is not None)) + 6 * (self.tone is not None))
+        return self.max_regions if self.hull else self._layout().tail
 
     def _blocks(self, text, g, packed):
         """group the labelled regions into blocks and filter those, in place -> (the blocks' [core counts | found, kept | table], in the
@@ -466,7 +466,7 @@ class TextEraser:
         labelled once more, for both stages (hull pixels carry no label), and that call's tensor rides behind ``packed``; otherwise the
         rows are the tail of ``packed`` itself and nothing rides in front."""
         if self.hull:
-            labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=self._route_tail())
+            labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=self._layout().tail)
             return labels, own, int(packed.numel())
         return self.last_labels, packed, 0
 
@@ -474,33 +474,32 @@ class TextEraser:
         """paint the flat regions and take them out of the text plane in place -> the painted page; ``mask_u8`` gets the mask of the whole
         plane.  ``route``: ``_route_labels``' triple; the core counts of the reduced plane are at the front of its tensor."""
         labels, own, _ = route
+        lay = self._layout(g.count)
         painted = torch.empty_like(page_d)
-        _flat_regions(page_d, text, labels, own, self.max_regions, self.flat_ring, self.flat, painted, mask_u8, g)
+        _flat_regions(page_d, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows("flat")], self.max_regions, self.flat_ring, self.flat,
+                      painted, mask_u8, g, own[lay.counts])
         return painted
 
     def _smooth(self, src, text, g, route, mask_u8):
         """fill the smooth regions harmonically and take them out of the text plane in place -> the filled page (a new buffer; ``src``:
         the page, or the flat stage's).  ``mask_u8``: the plane that gets the mask of the whole plane on entry, None where the flat stage
-        wrote the page's already.  The smooth rows ride behind the flat rows of ``route``'s tensor, the core counts at its front are
-        rewritten for the reduced plane."""
+        wrote the page's already.  The core counts at the front of ``route``'s tensor are rewritten for the reduced plane."""
         labels, own, _ = route
-        n, at = self.max_regions, g.count + 2 + 6 * self.max_regions + (5 * self.max_regions if self.flat is not None else 0)
+        lay = self._layout(g.count)
         painted = torch.empty_like(src)
-        _smooth_regions(src, text, labels, own[g.count + 2:], own[g.count:g.count + 2], own[at:at + 5 * n], n, self.smooth_ring, self.smooth,
-                        self.smooth_sweeps, painted, mask_u8, g, own[:g.count])
+        _smooth_regions(src, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows("smooth")], self.max_regions, self.smooth_ring,
+                        self.smooth, self.smooth_sweeps, painted, mask_u8, g, own[lay.counts])
         return painted
 
     def _tone(self, src, text, g, route, mask_u8):
         """fill the tone regions from one period away and take them out of the text plane in place -> the filled page (a new buffer;
         ``src``: the page, or the stage's before).  ``mask_u8``: the plane that gets the mask of the whole plane on entry, None where an
-        earlier stage wrote the page's already.  The tone rows ride behind the flat and smooth rows of ``route``'s tensor, the core counts
-        at its front are rewritten for the reduced plane."""
+        earlier stage wrote the page's already.  The core counts at the front of ``route``'s tensor are rewritten for the reduced plane."""
         labels, own, _ = route
-        n = self.max_regions
-        at = g.count + 2 + 6 * n + 5 * n * ((self.flat is not None) + (self.smooth is not None))
+        lay = self._layout(g.count)
         painted = torch.empty_like(src)
-        _tone_regions(src, text, labels, own[g.count + 2:], own[g.count:g.count + 2], own[at:at + 6 * n], n, self.tone_ring, self.tone_period,
-                      self.tone, painted, mask_u8, g, own[:g.count])
+        _tone_regions(src, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows("tone")], self.max_regions, self.tone_ring,
+                      self.tone_period, self.tone, painted, mask_u8, g, own[lay.counts])
         return painted
 
     def _run_filler(self, img, mplane, g):
@@ -566,20 +565,18 @@ class TextEraser:
                     counts = self._hulls(text, g, counts)
                 if self.routes:
                     route = self._route_labels(text, g, counts)
-                    if self.flat is not None:           # the first of the stages writes the page's mask; compose's, of the reduced plane, is scratch
-                        src = self._flat(page_d, text, g, route, mask_u8)
-                    if self.smooth is not None:
-                        src = self._smooth(src, text, g, route, None if self.flat is not None else mask_u8)
-                    if self.tone is not None:
-                        src = self._tone(src, text, g, route, None if src is not page_d else mask_u8)
-                    compose_mask = torch.empty_like(mask_u8)
+                    stages = [(self.flat, self._flat), (self.smooth, self._smooth), (self.tone, self._tone)]
+                    for k, stage in enumerate(run for on, run in stages if on is not None):     # each works on the page the one before left
+                        src = stage(src, text, g, route, None if k else mask_u8)
+                    compose_mask = torch.empty_like(mask_u8)        # the first enabled stage wrote the page's mask (later ones get None);
+                                                                    # compose's, of the reduced plane, is scratch
                     split = route[2]
                     counts = torch.cat([counts, route[1]]) if split else route[1]
                 if self.group is not None:              # members and the component count: the last words of the read-back
                     ride = int(blocks[0].numel())
                     counts = whole if counts is blocks[0] else torch.cat([counts, whole[ride:]])
             counts_h = all_h = counts.cpu().numpy()     # the one synchronisation before the download
-            flat_pixels = smooth_pixels = tone_pixels = 0
+            route_stats = {}                            # "flat_regions", "flat_pixels", ... of the enabled stages
             if self.regions:
                 if self.group is not None:
                     all_h, blocks_h = all_h[:-(self.max_regions + 1)], all_h[-(self.max_regions + 1):]
@@ -591,27 +588,13 @@ class TextEraser:
                     self.last_regions.update(members=members, components=components)
                 if self.hull:
                     self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
-                if self.routes:
-                    packed_h = all_h[split:]            # behind the hulls: the filled plane's own components; all that follows works on them
-                    counts_h, ftable, _, _, ftruncated = unpack_regions(packed_h, g.count, self.max_regions)
-                    gone, at = np.zeros(len(ftable), bool), g.count + 2 + 6 * self.max_regions
-                    if self.flat is not None:
-                        is_flat, colour, ring_pixels = unpack_flat(packed_h, g.count, self.max_regions, len(ftable))
-                        self.last_regions["flat"] = {"table": ftable, "is_flat": is_flat, "colour": colour, "ring_pixels": ring_pixels}
-                        flat_pixels = int(ftable[is_flat, 1].sum(dtype=np.int64))
-                        gone, at = gone | is_flat, at + 5 * self.max_regions
-                    if self.smooth is not None:         # a flat region has no text left: its smooth row is empty
-                        is_smooth, step, ring_pixels = unpack_smooth(packed_h[at:], len(ftable))
-                        self.last_regions["smooth"] = {"table": ftable, "is_smooth": is_smooth, "step": step, "ring_pixels": ring_pixels}
-                        smooth_pixels = int(ftable[is_smooth, 1].sum(dtype=np.int64))
-                        gone, at = gone | is_smooth, at + 5 * self.max_regions
-                    if self.tone is not None:           # a flat or smooth region has no text left: its tone row is empty
-                        is_tone, shift, err, step, ring_pixels = unpack_tone(packed_h[at:], len(ftable))
-                        self.last_regions["tone"] = {"table": ftable, "is_tone": is_tone, "shift": shift, "err": err, "step": step,
-                                                     "ring_pixels": ring_pixels}
-                        tone_pixels = int(ftable[is_tone, 1].sum(dtype=np.int64))
-                        gone = gone | is_tone
-                    table, truncated = ftable[~gone], ftruncated        # what pack plans its windows on
+                if self.routes:                         # behind the hulls: the filled plane's own components; all that follows works on them
+                    counts_h, ftable, truncated, stages, gone = unpack_routes(all_h[split:], self._layout(g.count))
+                    self.last_regions.update(stages)
+                    for name, stage in stages.items():
+                        route_stats[name + "_regions"] = int(stage["is_" + name].sum())
+                        route_stats[name + "_pixels"] = int(ftable[stage["is_" + name], 1].sum(dtype=np.int64))
+                    table = ftable[~gone]               # what pack plans its windows on
             selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
             any_text = bool(counts_h.sum() > 0)
             windows = self._plan(table, truncated, g, len(selected)) if (self.pack and any_text) else None
@@ -624,15 +607,10 @@ class TextEraser:
             else:
                 _compose_page_u8(src, text, out, slot, g, clean, compose_mask)
         self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0,
-                           "text_pixels": int(counts_h.sum()) + flat_pixels + smooth_pixels + tone_pixels}
+                           "text_pixels": int(counts_h.sum()) + sum(v for k, v in route_stats.items() if k.endswith("_pixels"))}
         if self.group is not None:
             self.last_stats.update(blocks=self.last_regions["kept"])
-        if self.flat is not None:
-            self.last_stats.update(flat_regions=int(is_flat.sum()), flat_pixels=flat_pixels)
-        if self.smooth is not None:
-            self.last_stats.update(smooth_regions=int(is_smooth.sum()), smooth_pixels=smooth_pixels)
-        if self.tone is not None:
-            self.last_stats.update(tone_regions=int(is_tone.sum()), tone_pixels=tone_pixels)
+        self.last_stats.update(route_stats)
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)

@@ -112,9 +112,13 @@ class TextBlocks(NamedTuple):
     components: int
 
 
+def _check_int_range(name, value, lo, hi):
+    if isinstance(value, bool) or int(value) != value or not lo <= value <= hi:
+        raise ValueError(f"{name} {value} must be an integer {lo}..{hi}")
+
+
 def check_block_args(gap):
-    if isinstance(gap, bool) or int(gap) != gap or not 1 <= gap <= 64:
-        raise ValueError(f"group gap {gap} must be an integer 1..64")
+    _check_int_range("group gap", gap, 1, 64)
 
 
 def check_region_args(connectivity, min_area, max_regions):
@@ -127,17 +131,13 @@ def check_region_args(connectivity, min_area, max_regions):
 
 
 def check_flat_args(tol, ring):
-    if isinstance(tol, bool) or int(tol) != tol or not 0 <= tol <= 255:
-        raise ValueError(f"flat tolerance {tol} must be an integer 0..255")
-    if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 8:
-        raise ValueError(f"flat ring {ring} must be an integer 1..8")
+    _check_int_range("flat tolerance", tol, 0, 255)
+    _check_int_range("flat ring", ring, 1, 8)
 
 
 def check_smooth_args(tol, ring, sweeps):
-    if isinstance(tol, bool) or int(tol) != tol or not 0 <= tol <= 255:
-        raise ValueError(f"smooth tolerance {tol} must be an integer 0..255")
-    if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 8:
-        raise ValueError(f"smooth ring {ring} must be an integer 1..8")
+    _check_int_range("smooth tolerance", tol, 0, 255)
+    _check_int_range("smooth ring", ring, 1, 8)
     try:
         check_sweeps(sweeps)
     except ValueError as e:
@@ -145,12 +145,31 @@ def check_smooth_args(tol, ring, sweeps):
 
 
 def check_tone_args(tol, ring, period):
-    if isinstance(tol, bool) or int(tol) != tol or not 0 <= tol <= 255:
-        raise ValueError(f"tone tolerance {tol} must be an integer 0..255")
-    if isinstance(ring, bool) or int(ring) != ring or not 1 <= ring <= 16:
-        raise ValueError(f"tone ring {ring} must be an integer 1..16")
-    if isinstance(period, bool) or int(period) != period or not 2 <= period <= 16:
-        raise ValueError(f"tone period {period} must be an integer 2..16")
+    _check_int_range("tone tolerance", tol, 0, 255)
+    _check_int_range("tone ring", ring, 1, 16)
+    _check_int_range("tone period", period, 2, 16)
+
+
+class RouteLayout:
+    """The words of the ONE int32 tensor the flat, smooth and tone stages leave for the read-back, ``[core counts (nt) | found, kept |
+    table (6 per row) | flat rows (5) | smooth rows (5) | tone rows (6)]`` with the rows of the enabled stages only: the only place that
+    knows the offsets.  ``counts``, ``n_regions``, ``table`` and ``rows(name)`` are slices that work on the device tensor and on its host
+    copy alike; ``tail``: the words behind the table, ``words``: all of them."""
+    ROW_WORDS = {"flat": 5, "smooth": 5, "tone": 6}     # in the order the stages run
+
+    def __init__(self, nt, max_regions, flat=False, smooth=False, tone=False):
+        self.nt, self.max_regions = int(nt), int(max_regions)
+        self.counts, self.n_regions = slice(0, self.nt), slice(self.nt, self.nt + 2)
+        self.table = slice(self.nt + 2, self.nt + 2 + 6 * self.max_regions)
+        self.stages = tuple(name for name, on in (("flat", flat), ("smooth", smooth), ("tone", tone)) if on)
+        at, self._rows = self.table.stop, {}
+        for name in self.stages:
+            self._rows[name] = slice(at, at + self.ROW_WORDS[name] * self.max_regions)
+            at = self._rows[name].stop
+        self.tail, self.words = at - self.table.stop, at
+
+    def rows(self, name):
+        return self._rows[name]
 
 
 def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
@@ -176,8 +195,8 @@ def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
 def _text_blocks(text, labels, counts, gap, min_area, max_regions, grid=None, tail=0):
     """``tsii_text_blocks`` in place on the device plane ``text``, behind the ``_text_regions`` call (``min_area=0``, same ``grid``) that
     left ``labels`` and the device pair ``counts`` = its {found, kept} -> (block_labels, packed, whole).  ``packed`` has the layout
-    ``_text_regions`` gives its own, ``[core counts | found, kept | table rows | tail words]``, of the BLOCKS: ``_region_hulls``,
-    ``_flat_regions`` and ``unpack_regions`` take it as it is.  It is the front of ``whole``, the ONE tensor a caller reads back:
+    ``_text_regions`` gives its own, ``[core counts | found, kept | table rows | tail words]``, of the BLOCKS: ``_region_hulls``
+    and ``unpack_regions`` take it as it is, the flat, smooth and tone stages its slices (``RouteLayout``).  It is the front of ``whole``, the ONE tensor a caller reads back:
     ``[packed | members (max_regions) | the components found]``."""
     h, w = int(text.shape[0]), int(text.shape[1])
     n = int(max_regions)
@@ -219,15 +238,14 @@ def _region_hulls(text, labels, packed, max_regions, grid=None):
          ptr(packed[:nt]) if nt else None, ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
 
 
-def _flat_regions(page, text, labels, packed, max_regions, ring, tol, painted, mask=None, grid=None):
-    """``tsii_flat_regions`` in place on the device plane ``text``, behind the ``_text_regions`` call that labelled THIS plane (same
-    ``grid``): ``packed`` is that call's tensor with a tail of ``5 * max_regions`` words right behind the table,
-    ``[core counts | found, kept | table | flat rows]``; the core counts at its front are rewritten for the reduced plane.  ``painted``
+def _flat_regions(page, text, labels, table, n_regions, rows, max_regions, ring, tol, painted, mask=None, grid=None, core_count=None):
+    """``tsii_flat_regions`` on the current stream, in place on the device plane ``text``: ``labels``, ``table`` (the device words of the
+    table) and ``n_regions`` (the device pair) as the ``_text_regions`` call that labelled THIS plane left them; ``rows``:
+    ``5 * max_regions`` device words for the flat rows; ``core_count`` (with ``grid``) is rewritten for the reduced plane.  ``painted``
     (and ``mask``, the 0 / 255 plane of the text on entry) are written."""
     h, w = int(text.shape[0]), int(text.shape[1])
-    nt = 0 if grid is None else grid.count
     n = int(max_regions)
-    assert packed.numel() >= nt + 2 + 11 * n and packed.dtype == torch.int32 and packed.device == text.device
+    assert rows.numel() == 5 * n and rows.dtype == torch.int32 and rows.device == text.device and rows.is_contiguous()
     assert page.shape == (h, w, 3) and painted.shape == (h, w, 3) and all(t.dtype == torch.uint8 and t.is_contiguous() for t in (page, painted))
     assert mask is None or (mask.shape == (h, w) and mask.dtype == torch.uint8 and mask.is_contiguous())
     nbytes = int(_lib.lib().tsii_flat_regions_ws_bytes(h, w, n))
@@ -235,8 +253,8 @@ def _flat_regions(page, text, labels, packed, max_regions, ring, tol, painted, m
         raise ValueError(f"text plane of {h} x {w} pixels is out of range")
     ws = ops._ws(nbytes, text)
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
-    call("tsii_flat_regions", ptr(page), ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, int(ring), int(tol),
-         tile, halo, ptr(packed[:nt]) if nt else None, ptr(painted), ptr(mask), ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+    call("tsii_flat_regions", ptr(page), ptr(text), ptr(labels), h, w, ptr(table), ptr(n_regions), n, int(ring), int(tol), tile, halo,
+         ptr(core_count) if grid is not None else None, ptr(painted), ptr(mask), ptr(rows), ptr(ws), _lib.stream())
 
 
 def _smooth_regions(page, text, labels, table, n_regions, rows, max_regions, ring, tol, sweeps, painted, mask=None, grid=None, core_count=None):
@@ -296,12 +314,28 @@ def unpack_smooth(rows_h, n):
     return rows[:, 0] != 0, rows[:, 1:4].astype(np.uint8), rows[:, 4].copy()
 
 
-def unpack_flat(packed_h, nt, max_regions, n):
-    """host copy of a ``packed`` with flat rows -> (is_flat bool ``[n]``, colour uint8 ``[n, 3]``, ring_pixels int32 ``[n]``) of the ``n``
-    table rows in use"""
-    at = nt + 2 + 6 * int(max_regions)
-    rows = packed_h[at:at + 5 * n].reshape(n, 5)
+def unpack_flat(rows_h, n):
+    """host copy of the flat rows -> (is_flat bool ``[n]``, colour uint8 ``[n, 3]``, ring_pixels int32 ``[n]``) of the ``n`` table rows in
+    use"""
+    rows = rows_h[:5 * n].reshape(n, 5)
     return rows[:, 0] != 0, rows[:, 1:4].astype(np.uint8), rows[:, 4].copy()
+
+
+def unpack_routes(own_h, layout):
+    """host copy of the stages' tensor -> (core counts, table, truncated, stages, gone).  ``stages``: per enabled stage the dict
+    ``TextEraser.last_regions`` carries under its name (``table`` and the stage's columns: ``is_flat`` / ``colour`` / ``ring_pixels``, ...);
+    ``gone``: bool per table row, some stage took the region out of the plane (it has no text left: its rows of the later stages are
+    empty)."""
+    counts_h, table, _, _, truncated = unpack_regions(own_h, layout.nt, layout.max_regions)
+    columns = {"flat": (unpack_flat, ("is_flat", "colour", "ring_pixels")),
+               "smooth": (unpack_smooth, ("is_smooth", "step", "ring_pixels")),
+               "tone": (unpack_tone, ("is_tone", "shift", "err", "step", "ring_pixels"))}
+    stages, gone = {}, np.zeros(len(table), bool)
+    for name in layout.stages:
+        unpack, names = columns[name]
+        stages[name] = dict(zip(names, unpack(own_h[layout.rows(name)], len(table))), table=table)
+        gone = gone | stages[name]["is_" + name]
+    return counts_h, table, truncated, stages, gone
 
 
 def unpack_hull_area(packed_h, nt, max_regions, n):
@@ -348,6 +382,15 @@ def fill_region_hulls(text, connectivity=8, min_area=0, max_regions=4096, device
     return RegionHulls(_like(plane * 255, text), TextRegions(_like(labels, text), table, found, kept, truncated), hull_area)
 
 
+def _page_and_plane(page_u8, mask_u8, device):
+    """the intake of the three fill functions: host or device arguments -> (page, plane) on one device, contiguous, the plane a copy"""
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
+        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
+    plane = _plane_on_device(mask_u8, device)
+    return p.to(plane.device).contiguous(), plane
+
+
 def flat_fill_regions(page_u8, mask_u8, tol, ring=3, connectivity=8, min_area=0, max_regions=4096, device=None) -> FlatFill:
     """Paint the text that sits on one flat colour.  ``page_u8``: ``[H, W, 3]`` uint8; ``mask_u8``: ``[H, W]`` uint8, non-zero = text (the
     255 masks ``TextEraser`` returns work directly); numpy or torch, host or device, neither is modified.  Regions below ``min_area`` are
@@ -358,18 +401,14 @@ def flat_fill_regions(page_u8, mask_u8, tol, ring=3, connectivity=8, min_area=0,
     of the counts, the table and the flat rows).  Host arguments are computed on ``device`` (default ``cuda:0``)."""
     check_region_args(connectivity, min_area, max_regions)
     check_flat_args(tol, ring)
-    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
-    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
-        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
-    plane = _plane_on_device(mask_u8, device)
-    page = p.to(plane.device).contiguous()
-    n = int(max_regions)
-    labels, packed = _text_regions(plane, connectivity, min_area, n, tail=5 * n)
+    page, plane = _page_and_plane(page_u8, mask_u8, device)
+    lay = RouteLayout(0, max_regions, flat=True)
+    labels, packed = _text_regions(plane, connectivity, min_area, lay.max_regions, tail=lay.tail)
     painted = torch.empty_like(page)
-    _flat_regions(page, plane, labels, packed, n, ring, tol, painted)
+    _flat_regions(page, plane, labels, packed[lay.table], packed[lay.n_regions], packed[lay.rows("flat")], lay.max_regions, ring, tol, painted)
     packed_h = packed.cpu().numpy()
-    _, table, found, kept, truncated = unpack_regions(packed_h, 0, n)
-    is_flat, colour, ring_pixels = unpack_flat(packed_h, 0, n, len(table))
+    _, table, found, kept, truncated = unpack_regions(packed_h, 0, lay.max_regions)
+    is_flat, colour, ring_pixels = unpack_flat(packed_h[lay.rows("flat")], len(table))
     return FlatFill(_like(painted, page_u8), _like(plane * 255, mask_u8), TextRegions(_like(labels, mask_u8), table, found, kept, truncated),
                     is_flat, colour, ring_pixels)
 
@@ -386,18 +425,15 @@ def smooth_fill_regions(page_u8, mask_u8, tol, ring=3, sweeps=8, connectivity=8,
     arguments are computed on ``device`` (default ``cuda:0``)."""
     check_region_args(connectivity, min_area, max_regions)
     check_smooth_args(tol, ring, sweeps)
-    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
-    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
-        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
-    plane = _plane_on_device(mask_u8, device)
-    page = p.to(plane.device).contiguous()
-    n = int(max_regions)
-    labels, packed = _text_regions(plane, connectivity, min_area, n, tail=5 * n)
+    page, plane = _page_and_plane(page_u8, mask_u8, device)
+    lay = RouteLayout(0, max_regions, smooth=True)
+    labels, packed = _text_regions(plane, connectivity, min_area, lay.max_regions, tail=lay.tail)
     painted = torch.empty_like(page)
-    _smooth_regions(page, plane, labels, packed[2:], packed[:2], packed[2 + 6 * n:], n, ring, tol, sweeps, painted)
+    _smooth_regions(page, plane, labels, packed[lay.table], packed[lay.n_regions], packed[lay.rows("smooth")], lay.max_regions, ring, tol, sweeps,
+                    painted)
     packed_h = packed.cpu().numpy()
-    _, table, _, _, _ = unpack_regions(packed_h, 0, n)
-    is_smooth, step, ring_pixels = unpack_smooth(packed_h[2 + 6 * n:], len(table))
+    _, table, _, _, _ = unpack_regions(packed_h, 0, lay.max_regions)
+    is_smooth, step, ring_pixels = unpack_smooth(packed_h[lay.rows("smooth")], len(table))
     return SmoothFill(_like(painted, page_u8), _like(plane * 255, mask_u8), table, is_smooth, step, ring_pixels)
 
 
@@ -415,18 +451,15 @@ def tone_fill_regions(page_u8, mask_u8, tol, ring=8, period=12, connectivity=8, 
     read-back of the counts, the table and the tone rows).  Host arguments are computed on ``device`` (default ``cuda:0``)."""
     check_region_args(connectivity, min_area, max_regions)
     check_tone_args(tol, ring, period)
-    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
-    if p.dim() != 3 or p.dtype != torch.uint8 or tuple(p.shape) != tuple(mask_u8.shape[:2]) + (3,):
-        raise ValueError(f"page must be [H, W, 3] uint8 for a mask of {tuple(mask_u8.shape)}, got {tuple(p.shape)} {p.dtype}")
-    plane = _plane_on_device(mask_u8, device)
-    page = p.to(plane.device).contiguous()
-    n = int(max_regions)
-    labels, packed = _text_regions(plane, connectivity, min_area, n, tail=6 * n)
+    page, plane = _page_and_plane(page_u8, mask_u8, device)
+    lay = RouteLayout(0, max_regions, tone=True)
+    labels, packed = _text_regions(plane, connectivity, min_area, lay.max_regions, tail=lay.tail)
     painted = torch.empty_like(page)
-    _tone_regions(page, plane, labels, packed[2:], packed[:2], packed[2 + 6 * n:], n, ring, period, tol, painted)
+    _tone_regions(page, plane, labels, packed[lay.table], packed[lay.n_regions], packed[lay.rows("tone")], lay.max_regions, ring, period, tol,
+                  painted)
     packed_h = packed.cpu().numpy()
-    _, table, _, _, _ = unpack_regions(packed_h, 0, n)
-    is_tone, shift, err, step, ring_pixels = unpack_tone(packed_h[2 + 6 * n:], len(table))
+    _, table, _, _, _ = unpack_regions(packed_h, 0, lay.max_regions)
+    is_tone, shift, err, step, ring_pixels = unpack_tone(packed_h[lay.rows("tone")], len(table))
     return ToneFill(_like(painted, page_u8), _like(plane * 255, mask_u8), table, is_tone, shift, err, step, ring_pixels)
 
 
@@ -455,16 +488,8 @@ def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None
     dropped.  ``labels`` comes back the same kind and on the same device as ``text``; one synchronisation (the read-back of the
     counts and the table).  A host plane is computed on ``device`` (default ``cuda:0``)."""
     check_region_args(connectivity, min_area, max_regions)
-    t = torch.from_numpy(np.ascontiguousarray(text)) if isinstance(text, np.ndarray) else text
-    if t.dim() != 2 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"text must be [H, W] uint8, got {tuple(t.shape)} {t.dtype}")
-    dev = torch.device(device) if device is not None else (t.device if t.is_cuda else torch.device("cuda:0"))
-    plane = t.to(dev, copy=True).contiguous()
+    plane = _plane_on_device(text, device)
     labels, packed = _text_regions(plane, connectivity, min_area, max_regions)
     _, table, found, kept, truncated = unpack_regions(packed.cpu().numpy(), 0, max_regions)
-    if isinstance(text, np.ndarray):
-        labels = labels.cpu().numpy()
-    elif labels.device != text.device:
-        labels = labels.to(text.device)
-    return TextRegions(labels, table, found, kept, truncated)
+    return TextRegions(_like(labels, text), table, found, kept, truncated)
 

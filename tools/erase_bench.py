@@ -282,23 +282,11 @@ def main(argv=None):
                     region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h[:split] if split else packed_h, g.count, args.max_regions,
                                                                          len(table)).sum(dtype=np.int64))
                 if with_routes:                             # everything behind works on these stages' own components and counts
-                    own = packed_h[split:]
-                    packed_h = packed_h[:split] if split else packed_h
-                    counts_h, ftable, _, _, truncated = RG.unpack_regions(own, g.count, args.max_regions)
-                    gone, at = np.zeros(len(ftable), bool), g.count + 2 + 6 * args.max_regions
+                    counts_h, ftable, truncated, route_stages, gone = RG.unpack_routes(packed_h[split:], eraser._layout(g.count))
                     region_info.update(labelled=len(ftable))
-                    if with_flat:
-                        is_flat = RG.unpack_flat(own, g.count, args.max_regions, len(ftable))[0]
-                        region_info.update(flat_regions=int(is_flat.sum()), flat_pixels=int(ftable[is_flat, 1].sum(dtype=np.int64)))
-                        gone, at = gone | is_flat, at + 5 * args.max_regions
-                    if with_smooth:
-                        is_smooth = RG.unpack_smooth(own[at:], len(ftable))[0]
-                        region_info.update(smooth_regions=int(is_smooth.sum()), smooth_pixels=int(ftable[is_smooth, 1].sum(dtype=np.int64)))
-                        gone, at = gone | is_smooth, at + 5 * args.max_regions
-                    if with_tone:
-                        is_tone = RG.unpack_tone(own[at:], len(ftable))[0]
-                        region_info.update(tone_regions=int(is_tone.sum()), tone_pixels=int(ftable[is_tone, 1].sum(dtype=np.int64)))
-                        gone = gone | is_tone
+                    for name, stage in route_stages.items():
+                        is_ = stage["is_" + name]
+                        region_info.update({name + "_regions": int(is_.sum()), name + "_pixels": int(ftable[is_, 1].sum(dtype=np.int64))})
                     table = ftable[~gone]
             selected = [t for t in range(g.count) if counts_h[t] > 0]
             windows, plan_ms = None, 0.0
