@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 16
+#define TSII_ABI_VERSION 17
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -919,6 +919,43 @@ size_t tsii_tone_regions_ws_bytes(int h, int w, int max_regions, int period);
 int tsii_tone_regions(const uint8_t* page, uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
                       int max_regions, int ring, int period, int tol, int tile, int halo, int* core_count,
                       uint8_t* painted, uint8_t* mask, int* tone, void* ws, void* stream);
+
+/* ---- K18: page scores (csrc/score.hip) -- what TextEraser did to a page, measured against the same page cleaned by hand: the text mask of
+ * a (raw, clean) pair as the reference's training data derives it (Dataloader.py:213-222), and the eraser's errors over the page, over
+ * what it filled, over what it left, and per region.  All in integers: exact, the same bits on every run.
+ *
+ * tsii_pair_text_mask: raw, clean uint8 [h,w,3]; truth uint8 [h,w] (none of the two pages); thr 0..255; k 1..31, even values included.
+ *   L(p)   = (19595 R + 38470 G + 7471 B + 32768) >> 16: Pillow's convert("L")
+ *   t(p)   = |L_raw(p) - L_clean(p)| > thr
+ *   truth(y,x) = 255 iff t(y + oy, x + ox) holds for some oy, ox in [-(k/2), k - 1 - (k/2)] (integer division) with (y + oy, x + ox) on
+ *            the page, else 0: cv2.dilate with a k x k kernel of ones, its default anchor and a border that never sets a pixel.  k = 10
+ *            is the reference's: offsets -5..+4.
+ *   One launch; the thresholded plane lives in LDS only.
+ *
+ * tsii_page_scores: out (the eraser's page), clean (the hand-cleaned page) uint8 [h,w,3]; mask (the eraser's, non-zero = text), truth
+ * uint8 [h,w]; labels int32 [h,w] or NULL; table int32 [n_rows,6] ON THE DEVICE, of which only the label column is read and which ascends
+ * in it (as every tsii_*_regions kernel assumes); n_rows >= 0, a HOST count.  With d_c(p) = |out[p][c] - clean[p][c]|:
+ *   a(p) = sum_c d_c,  s(p) = sum_c d_c^2,  m(p) = max_c d_c
+ *   page, int64 [12] = { tp, fp, fn, tn of (mask != 0) against (truth != 0);
+ *                        pixels, sum a, sum s, max m over the pixels with mask != 0 (the FILL);
+ *                        the same four over the pixels with mask == 0 (the LEFTOVER: the eraser returns the page there, so this is the
+ *                        ink the mask missed) }.  A maximum over no pixel is 0.
+ *   rows, int64 [n_rows,4]: row r = { pixels, sum a, sum s, max m } over the pixels whose label is table[r][0], whatever their mask byte.
+ *            A label that is 0 or not in the table counts in no row; a row whose label does not occur is all zero.  With labels == NULL or
+ *            n_rows == 0 only `page` is written, and table and rows may be NULL.
+ *   The call clears what it accumulates into: a second call on the same buffers gives the same bytes.  All inputs are read only.
+ * The largest sum, 3 * 255^2 * (2^31 - 2), fits int64.  No allocation, no host synchronisation, everything on the caller's stream; no
+ * grid-wide barrier and no waiting on another block; 64-bit atomicAdd and 32-bit atomicMax on `rows` only.
+ * ws: tsii_page_scores_ws_bytes(h, w, max_rows) bytes (0: refused), 4-byte aligned; any n_rows <= max_rows may use it; it needs nothing
+ * cleared beforehand and holds nothing a later call depends on (12 words per block of 64 x 32 pixels).  page and rows: 8-byte aligned.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1; h*w > 2^31 - 2; thr, k or n_rows (max_rows) out of range; a NULL
+ * among raw, clean, truth / out, clean, mask, truth, page, ws (table, rows: only with labels and n_rows > 0); truth == raw or clean;
+ * ws_bytes below tsii_page_scores_ws_bytes; a misaligned ws, page or rows.  A row found by the search lies below n_rows and nothing is
+ * indexed by a label: a table that does not belong to the labels gives wrong numbers, never an access outside the buffers. */
+int tsii_pair_text_mask(const uint8_t* raw, const uint8_t* clean, int h, int w, int thr, int k, uint8_t* truth, void* stream);
+size_t tsii_page_scores_ws_bytes(int h, int w, int max_rows);
+int tsii_page_scores(const uint8_t* out, const uint8_t* clean, const uint8_t* mask, const uint8_t* truth, const int* labels,
+                     const int* table, int n_rows, int h, int w, int64_t* page, int64_t* rows, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -1,0 +1,324 @@
+"""``pair_text_mask``, ``score_page``, ``EraserMetrics`` and ``evaluate_eraser`` (text_segmentation_image_inpainting_amd/score.py) over
+``TextEraser`` with the stand-in nets of ``tests/test_text_eraser.py`` (and the constant-colour filler of
+``tests/test_text_eraser_working_resolution.py``, whose error can be written down by hand), on pages of 150 x 217 pixels with tiles of 64
+and a halo of 8.
+
+Every integer ``compute()`` returns is EQUAL to the restatement of ``tests/test_score_kernels.py`` applied to what the eraser itself
+returned -- its page, its mask, the label plane and the table its routes worked on -- and every ratio to ``metrics._ratio`` of those
+integers.  The eraser is not disturbed: the same bytes before and after an ``update``, ``last_route_labels`` the very plane the stages were
+given, and no device-to-host copy in ``update`` outside the eraser's own call.  The cases run on the emulator (CPU suite) and, with -m gpu,
+on the chip.
+"""
+import numpy as np
+import pytest
+import torch
+
+import text_segmentation_image_inpainting_amd as T
+from tests.backends import BACKENDS, both_backends
+from tests.test_score_kernels import pair_ref, score_ref
+from tests.test_text_eraser import MEAN, STD, standin_filler, standin_segmenter, to_byte
+from tests.test_text_eraser_working_resolution import COLOUR
+from tests.test_text_eraser_working_resolution import standin_filler as colour_filler
+from tests.test_text_eraser_working_resolution import standin_segmenter as pixel_segmenter
+from text_segmentation_image_inpainting_amd.metrics import _ratio
+from text_segmentation_image_inpainting_amd.score import ROUTES
+
+H, W = 150, 217
+TILE, HALO, DILATE, MAXR = 64, 8, 3, 32
+DISC = (90, 160, 230)
+VARIANTS = {"default": {}, "regions": dict(regions=True), "flat": dict(flat=0), "hull_flat": dict(hull=True, flat=0),
+            "all_routes": dict(flat=0, smooth=8, tone=8, group=4)}
+
+
+def make_pair(seed):
+    """(raw, clean): noisy bright paper with a disc of one colour; the raw page has a dark block on the disc (a uniform bubble) and a dark
+    U, which is not convex, directly on the noise, a little further down the page with every seed"""
+    rng = np.random.default_rng(seed)
+    clean = rng.integers(200, 256, size=(H, W, 3), dtype=np.uint8)
+    yy, xx = np.mgrid[0:H, 0:W]
+    clean[(yy - 40) ** 2 + (xx - 50) ** 2 <= 32 * 32] = DISC
+    raw = clean.copy()
+    dark = lambda shape: rng.integers(0, 40, size=shape + (3,), dtype=np.uint8)
+    raw[35:46, 42:57] = dark((11, 15))
+    y0 = 95 + 3 * seed
+    u = np.zeros((H, W), bool)
+    u[y0:y0 + 25, 120:160] = True
+    u[y0:y0 + 17, 130:150] = False
+    raw[u] = dark((int(u.sum()),))
+    return raw, clean
+
+
+class Recorder(T.TextEraser):
+    """a TextEraser that keeps, per page, host copies of what it returned and left behind"""
+
+    def __init__(self, *a, **k):
+        super().__init__(*a, **k)
+        self.seen = []
+
+    def __call__(self, page):
+        out, mask = super().__call__(page)
+        labels = self.last_route_labels if self.routes else self.last_labels
+        host = lambda t: t.cpu().numpy().copy() if isinstance(t, torch.Tensor) else np.array(t)
+        self.seen.append(dict(out=host(out), mask=host(mask), labels=None if labels is None else host(labels), stats=dict(self.last_stats),
+                              regions=self.last_regions))
+        return out, mask
+
+
+def make_eraser(dev, filler=standin_filler, cls=Recorder, **kw):
+    """with a route on, the per-pixel segmenter: every dark pixel is text, so that the ring around the block on the disc is the disc's own
+    colour; otherwise the segmenter of shifted taps, which misses ink at the glyphs' edges"""
+    routed = any(kw.get(name) is not None for name in ("flat", "smooth", "tone"))
+    return cls(pixel_segmenter if routed else standin_segmenter, filler, mean=MEAN, std=STD, tile=TILE, halo=HALO, dilate=DILATE, tile_batch=3,
+               device=dev, max_regions=MAXR, **kw)
+
+
+def routes_ref(pages, code):
+    """(regions, pixels, sum a, sum s) of one route over the pages' rows"""
+    mine = [p["rows"][p["route"] == code] for p in pages]
+    return (sum(len(m) for m in mine),) + tuple(int(sum(m[:, c].sum() for m in mine)) for c in range(3))
+
+
+def same(a, b):
+    """floats equal, nan equal to nan"""
+    return a == b or (np.isnan(a) and np.isnan(b))
+
+
+# ---- the two functions --------------------------------------------------------------------------------------------------------------
+@both_backends
+def test_pair_text_mask_kinds(backend):
+    """numpy in, numpy out; torch in, torch out, on the argument's device; the bytes of the restatement"""
+    raw, clean = make_pair(0)
+    with BACKENDS[backend]() as dev:
+        got_np = T.pair_text_mask(raw, clean, device=dev)
+        got_host = T.pair_text_mask(torch.from_numpy(raw), torch.from_numpy(clean), device=dev)
+        got_dev = T.pair_text_mask(torch.from_numpy(raw).to(dev), torch.from_numpy(clean).to(dev), device=None if backend == "gpu" else dev)
+        tight = T.pair_text_mask(raw, clean, brightness_difference=0.1, dilate=3, device=dev)
+        dev_host = got_dev.cpu().numpy()
+    assert isinstance(got_np, np.ndarray) and got_np.dtype == np.uint8 and np.array_equal(got_np, pair_ref(raw, clean, 102, 10))
+    assert isinstance(got_host, torch.Tensor) and got_host.device.type == "cpu" and np.array_equal(got_host.numpy(), got_np)
+    assert isinstance(got_dev, torch.Tensor) and got_dev.device == torch.device(dev) and np.array_equal(dev_host, got_np)
+    assert np.array_equal(tight, pair_ref(raw, clean, 25, 3)) and got_np.any() and not got_np.all()
+    for kw in (dict(brightness_difference=-0.1), dict(brightness_difference=1.5), dict(dilate=0), dict(dilate=32), dict(dilate=2.5)):
+        with pytest.raises(ValueError):
+            T.pair_text_mask(raw, clean, device="cpu", **kw)
+    with pytest.raises(ValueError):
+        T.pair_text_mask(raw, clean[:, :-1], device="cpu")
+
+
+@both_backends
+def test_score_page(backend):
+    """the arrays of the kernel test's restatement, from numpy and from torch; labels and table come together"""
+    raw, clean = make_pair(1)
+    with BACKENDS[backend]() as dev:
+        truth = T.pair_text_mask(raw, clean, device=dev)
+        regions = T.text_regions(truth, device=dev)
+        got = T.score_page(raw, clean, truth, truth, regions.labels, regions.table, device=dev)
+        plain = T.score_page(torch.from_numpy(raw).to(dev), torch.from_numpy(clean).to(dev), torch.from_numpy(truth).to(dev),
+                             torch.from_numpy(truth).to(dev), device=None if backend == "gpu" else dev)
+    page, rows = score_ref(raw, clean, truth, truth, regions.labels, regions.table)
+    assert len(rows) == 2 and got["page"].dtype == got["rows"].dtype == np.int64
+    assert np.array_equal(got["page"], page) and np.array_equal(got["rows"], rows)
+    assert np.array_equal(plain["page"], page) and plain["rows"].shape == (0, 4)
+    assert page[1] == page[2] == 0 and page[9] == 0, "the mask is the truth: the pages differ inside it only"
+    with pytest.raises(ValueError, match="together"):
+        T.score_page(raw, clean, truth, truth, labels=regions.labels, device="cpu")
+
+
+# ---- evaluate_eraser ------------------------------------------------------------------------------------------------------------------
+@both_backends
+@pytest.mark.parametrize("variant", list(VARIANTS))
+def test_evaluate_eraser_equals_the_restatement(backend, variant):
+    pairs = [make_pair(0), make_pair(1)]
+    with BACKENDS[backend]() as dev:
+        eraser = make_eraser(dev, **VARIANTS[variant])
+        res = T.evaluate_eraser(eraser, pairs, T.EraserMetrics(ssim=(variant == "flat")))
+    assert len(res["pages"]) == len(eraser.seen) == 2
+    total = np.zeros(12, np.int64)
+    for (raw, clean), seen, got in zip(pairs, eraser.seen, res["pages"]):
+        reg = seen["regions"]
+        table = np.zeros((0, 6), np.int32) if reg is None else (reg["flat"]["table"] if "flat" in reg else reg["table"])
+        page, rows = score_ref(seen["out"], clean, seen["mask"], pair_ref(raw, clean, 102, 10), seen["labels"], table)
+        assert np.array_equal(got["page"], page), (got["page"], page)
+        assert np.array_equal(got["rows"], rows) and np.array_equal(got["table"], table)
+        assert len(rows) == (0 if variant == "default" else 2) and (variant == "default" or (rows[:, 0] > 0).all())
+        route = np.full(len(table), ROUTES.index("net"))
+        for name in ("tone", "smooth", "flat"):
+            if reg is not None and name in reg:
+                route[reg[name]["is_" + name]] = ROUTES.index(name)
+        assert np.array_equal(got["route"], route)
+        assert page[8] == H * W - page[4]
+        assert (page[9] > 0) == (variant in ("default", "regions")), "the segmenter of shifted taps misses ink at the glyphs' edges: a leftover error"
+        total += page
+    tp, fp, fn, tn = (int(v) for v in total[:4])
+    assert [res["mask"][k] for k in ("tp", "fp", "fn", "tn")] == [tp, fp, fn, tn] and tp + fp + fn + tn == 2 * H * W and min(tp, fn, tn) > 0   # the truth is grown by 10
+    assert res["mask"]["precision"] == float(_ratio(tp, tp + fp)) and res["mask"]["recall"] == float(_ratio(tp, tp + fn))
+    assert res["mask"]["f1"] == float(_ratio(2 * tp, 2 * tp + fp + fn)) and res["mask"]["iou"] == float(_ratio(tp, tp + fp + fn))
+    for name, at in (("fill", 4), ("leftover", 8)):
+        n, a, s = (int(v) for v in total[at:at + 3])
+        assert res[name]["pixels"] == n and res[name]["l1"] == float(_ratio(a, 765 * n))
+        with np.errstate(divide="ignore"):
+            assert res[name]["psnr"] == float(10.0 * np.log10(255.0 ** 2 / _ratio(s, 3 * n)))
+        assert res[name]["max"] == max(int(p["page"][at + 3]) for p in res["pages"])
+    for code, name in enumerate(ROUTES):
+        regions, n, a, s = routes_ref(res["pages"], code)
+        got = res["routes"][name]
+        assert (got["regions"], got["pixels"]) == (regions, n) and same(got["l1"], float(_ratio(a, 765 * n)))
+        with np.errstate(divide="ignore", invalid="ignore"):
+            assert same(got["psnr"], float(10.0 * np.log10(255.0 ** 2 / _ratio(s, 3 * n))))
+        means = [(float(r[1]) / (765 * float(r[0])), i, k) for i, p in enumerate(res["pages"]) for k, r in enumerate(p["rows"])
+                 if p["route"][k] == code and r[0] > 0]
+        if means:
+            top = max(m[0] for m in means)
+            assert got["worst"]["l1"] == top and (top, got["worst"]["page"], got["worst"]["row"]) in means
+        else:
+            assert got["worst"] is None
+    if variant == "flat":                                  # glyphs on a uniform bubble, flat=0: painted with the bubble's own colour
+        flat = res["routes"]["flat"]
+        assert flat["regions"] == 2 and flat["l1"] == 0.0 and flat["psnr"] == float("inf")
+        assert flat["pixels"] == sum(s["stats"]["flat_pixels"] for s in eraser.seen) > 0
+        assert res["routes"]["net"]["regions"] == 2 and res["routes"]["net"]["l1"] > 0
+        assert 0.0 < res["ssim"] < 1.0 and res["ssim"] == float(np.mean([p["ssim"] for p in res["pages"]]))
+    else:
+        assert "ssim" not in res
+    if variant == "default":
+        assert all(res["routes"][name]["regions"] == 0 and np.isnan(res["routes"][name]["l1"]) for name in ROUTES)
+    if variant == "regions":
+        assert res["routes"]["net"]["regions"] == 4 and res["routes"]["flat"]["regions"] == 0
+
+
+@both_backends
+def test_constant_filler_by_hand(backend):
+    """the filler paints one colour: the net's error is that colour against the hand-cleaned paper, written down here; the flat route
+    repairs its region exactly"""
+    raw, clean = make_pair(2)
+    colour = to_byte(np.asarray(COLOUR, np.float32)).astype(np.int64)
+    assert colour.tolist() == [64, 128, 191]
+    with BACKENDS[backend]() as dev:
+        eraser = make_eraser(dev, filler=colour_filler, flat=0)
+        res = T.evaluate_eraser(eraser, [(raw, clean)])
+    seen, page = eraser.seen[0], res["pages"][0]
+    assert page["route"].tolist() == [ROUTES.index("flat"), ROUTES.index("net")]
+    net = seen["labels"] == page["table"][1][0]
+    d = np.abs(colour - clean[net].astype(np.int64))
+    assert res["routes"]["net"]["pixels"] == int(net.sum()) > 25 * 40 - 17 * 20
+    assert res["routes"]["net"]["l1"] == d.sum() / (765.0 * net.sum())
+    assert res["routes"]["net"]["psnr"] == 10.0 * np.log10(255.0 ** 2 / ((d * d).sum() / (3.0 * net.sum())))
+    assert res["routes"]["net"]["worst"] == {"l1": res["routes"]["net"]["l1"], "page": 0, "row": 1}
+    assert res["routes"]["flat"]["l1"] == 0.0 and res["routes"]["flat"]["pixels"] == seen["stats"]["flat_pixels"]
+    assert res["fill"]["max"] == int(d.max()) and res["fill"]["pixels"] == int((seen["mask"] != 0).sum())
+
+
+# ---- the eraser is not disturbed ----------------------------------------------------------------------------------------------------------
+@both_backends
+def test_the_eraser_is_undisturbed(backend):
+    raw, clean = make_pair(0)
+    with BACKENDS[backend]() as dev:
+        default = make_eraser(dev, cls=T.TextEraser)
+        before = default(raw)
+        metrics = T.EraserMetrics()
+        metrics.update(default, raw, clean)
+        after = default(raw)
+        assert default.last_route_labels is None and default.last_labels is None
+        with_regions = make_eraser(dev, cls=T.TextEraser, regions=True)
+        with_regions(raw)
+        assert with_regions.last_route_labels is None and with_regions.last_labels is not None
+        routed = make_eraser(dev, cls=T.TextEraser, hull=True, flat=0)
+        given, real = [], routed._flat
+        routed._flat = lambda src, text, g, route, mask_u8: (given.append(route[0]), real(src, text, g, route, mask_u8))[1]
+        first = routed(raw)
+        assert len(given) == 1 and routed.last_route_labels is given[0]
+        metrics.update(routed, raw, clean)
+        assert len(given) == 2 and routed.last_route_labels is given[1]
+        second = routed(raw)
+        own, hulls = routed.last_route_labels.cpu().numpy(), routed.last_labels.cpu().numpy()
+        plain = make_eraser(dev, cls=T.TextEraser, flat=0)
+        plain(raw)
+        assert plain.last_route_labels is plain.last_labels, "without hulls the stages work on the first labelling"
+    assert all(np.array_equal(x, y) for x, y in zip(before + first, after + second))
+    assert own.dtype == np.int32 and own.shape == (H, W)
+    assert ((hulls != 0) <= (own != 0)).all() and ((own != 0) & (hulls == 0)).sum() > 100, "the hull of the U carries labels of the second labelling only"
+    assert len(metrics.compute()["pages"]) == 2
+
+
+@pytest.mark.gpu
+def test_update_makes_no_device_to_host_transfer_of_its_own(monkeypatch):
+    """``update()`` only enqueues: outside the eraser's own call (which synchronises once per page, as it always does) the host neither
+    reads anything back nor waits for the stream until ``compute()``.  The two guards of ``tests/test_metrics_api.py``, both lifted while
+    the eraser itself runs: ``torch.cuda.set_sync_debug_mode("error")`` where this torch build honours it (probed with an ``item()`` that
+    must raise) -- it also catches a blocking upload, such as the region table's from pageable memory would be -- and spies on
+    ``Tensor.cpu / item / tolist / numpy`` in any case."""
+    raw, clean = make_pair(0)
+    with BACKENDS["gpu"]() as dev:
+        raw_d, clean_d = torch.from_numpy(raw).to(dev), torch.from_numpy(clean).to(dev)
+        inside, guard = [], {"mode": "default"}
+
+        class Marked(T.TextEraser):
+            def __call__(self, page):
+                inside.append(True)
+                torch.cuda.set_sync_debug_mode("default")
+                try:
+                    return super().__call__(page)
+                finally:
+                    inside.pop()
+                    torch.cuda.set_sync_debug_mode(guard["mode"])
+
+        eraser = make_eraser(dev, cls=Marked, flat=0)
+        metrics = T.EraserMetrics(ssim=True)
+        metrics.update(eraser, raw_d, clean_d)               # warm-up: library load, first-call allocations
+        torch.cuda.synchronize()
+        torch.cuda.set_sync_debug_mode("error")
+        try:
+            try:
+                torch.ones(1, device=dev).item()
+                honoured = False
+            except RuntimeError:
+                honoured = True
+        finally:
+            torch.cuda.set_sync_debug_mode("default")
+        print("set_sync_debug_mode('error') honoured by this build: %s" % honoured)
+        reads = []
+        with monkeypatch.context() as mp:
+            for name in ("cpu", "item", "tolist", "numpy"):
+                real = getattr(torch.Tensor, name)
+
+                def spy(self, *a, _real=real, _name=name, **k):
+                    if not inside:
+                        reads.append(_name)
+                    return _real(self, *a, **k)
+                mp.setattr(torch.Tensor, name, spy)
+            if honoured:
+                guard["mode"] = "error"
+                torch.cuda.set_sync_debug_mode("error")
+            try:
+                for _ in range(2):
+                    metrics.update(eraser, raw_d, clean_d)
+            finally:
+                guard["mode"] = "default"
+                torch.cuda.set_sync_debug_mode("default")
+            assert reads == [], reads
+            res = metrics.compute()
+            assert reads.count("cpu") == 1, reads
+    assert len(res["pages"]) == 3 and np.array_equal(res["pages"][0]["page"], res["pages"][2]["page"])
+    assert len(res["pages"][2]["rows"]) == 2, "the table was uploaded: two regions scored"
+
+
+@pytest.mark.gpu
+def test_evaluate_example_eraser_gpu(capsys):
+    """examples/evaluate.py --task eraser --synthetic: one JSON line whose counts add up to the pages' pixels"""
+    import importlib.util
+    import json
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("evaluate_example", os.path.join(root, "examples", "evaluate.py"))
+    demo = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(demo)
+    with BACKENDS["gpu"]():
+        demo.main(["--task", "eraser", "--synthetic", "2", "--synthetic-size", "300", "420", "--tile", "256", "--halo", "32", "--flat", "8", "--ssim"])
+    def not_strict(name):
+        raise AssertionError("%s in the JSON line: strict parsers reject it" % name)
+    line = json.loads(capsys.readouterr().out.strip().splitlines()[-1], parse_constant=not_strict)
+    assert demo.strict_json({"a": [float("nan"), float("inf"), 1.5], "b": 2}) == {"a": [None, "inf", 1.5], "b": 2}
+    assert line["routes"]["smooth"]["l1"] is None and line["routes"]["smooth"]["regions"] == 0, "no smooth route: a ratio over nothing"
+    assert line["task"] == "eraser" and line["pages"] == 2 and sorted(line["routes"]) == sorted(ROUTES)
+    assert sum(line["mask"][k] for k in ("tp", "fp", "fn", "tn")) == 2 * 300 * 420 and line["mask"]["tp"] + line["mask"]["fn"] > 0
+    assert line["fill"]["pixels"] + line["leftover"]["pixels"] == 2 * 300 * 420 and -1.0 <= line["ssim"] <= 1.0

@@ -17,3 +17,4 @@ from .regions import (FlatFill, RegionHulls, SmoothFill, TextBlocks, TextRegions
                       fill_region_hulls, flat_fill_regions, smooth_fill_regions, text_blocks, text_regions, tone_fill_regions)
 from .fill import HarmonicFill, harmonic_fill  # noqa: F401,E402
 from .metrics import InpaintingMetrics, SegmentationMetrics, evaluate_inpainting, evaluate_segmentation  # noqa: F401,E402
+from .score import EraserMetrics, evaluate_eraser, pair_text_mask, score_page  # noqa: F401,E402

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 16          # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 17          # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -182,6 +182,10 @@ SIGNATURES = {
     # K17 tone regions (csrc/tone.hip): the text plane in place behind K13 / K16, int32 tone rows; ws 4-byte aligned
     "tsii_tone_regions_ws_bytes": (_z, [_i, _i, _i, _i]),
     "tsii_tone_regions": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    # K18 page scores (csrc/score.hip): uint8 pages and planes, int32 labels / table, int64 page sums and rows; ws 4-byte aligned
+    "tsii_pair_text_mask": (_i, [_p, _p, _i, _i, _i, _i, _p, _p]),
+    "tsii_page_scores_ws_bytes": (_z, [_i, _i, _i]),
+    "tsii_page_scores": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _p, _p, _p, _z, _p]),
 }
 
 _LIB = None

@@ -403,6 +403,7 @@ class TextEraser:
         self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks"; + "smooth_regions", "smooth_pixels"; + "tone_regions", "tone_pixels")
         self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components"; + "smooth"; + "tone")
         self.last_labels = None                         # its int32 label plane, left on the device
+        self.last_route_labels = None                   # the int32 label plane the flat, smooth and tone stages worked on (``_route_labels``), left on the device; None unless one of them is enabled
 
     # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
     def _upload(self, page):
@@ -565,6 +566,7 @@ class TextEraser:
                     counts = self._hulls(text, g, counts)
                 if self.routes:
                     route = self._route_labels(text, g, counts)
+                    self.last_route_labels = route[0]
                     stages = [(self.flat, self._flat), (self.smooth, self._smooth), (self.tone, self._tone)]
                     for k, stage in enumerate(run for on, run in stages if on is not None):     # each works on the page the one before left
                         src = stage(src, text, g, route, None if k else mask_u8)
