@@ -223,8 +223,8 @@ def test_the_eraser_is_undisturbed(backend):
         with_regions(raw)
         assert with_regions.last_route_labels is None and with_regions.last_labels is not None
         routed = make_eraser(dev, cls=T.TextEraser, hull=True, flat=0)
-        given, real = [], routed._flat
-        routed._flat = lambda src, text, g, route, mask_u8: (given.append(route[0]), real(src, text, g, route, mask_u8))[1]
+        given, real = [], routed._route
+        routed._route = lambda name, src, text, g, labels, own, mask_u8: (given.append(labels), real(name, src, text, g, labels, own, mask_u8))[1]
         first = routed(raw)
         assert len(given) == 1 and routed.last_route_labels is given[0]
         metrics.update(routed, raw, clean)

@@ -29,6 +29,7 @@ With ``group`` the regions are first grouped into blocks of lettering on the dev
 filter, the hulls, the flat stage and ``pack`` then judge, fill, paint and place whole blocks instead of single glyphs.
 """
 from contextlib import contextmanager
+from dataclasses import dataclass
 from typing import NamedTuple
 
 import numpy as np
@@ -39,9 +40,8 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import (RouteLayout, _flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args,
-                      check_flat_args, check_region_args, check_smooth_args, check_tone_args, unpack_blocks, unpack_hull_area, unpack_regions,
-                      unpack_routes)
+from .regions import (ReadBack, _flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args,
+                      check_flat_args, check_region_args, check_smooth_args, check_tone_args)
 
 
 class TileGrid(NamedTuple):
@@ -227,13 +227,19 @@ def _page_resize_u8(page, hs, ws):
     return out
 
 
+def _page_tensor(page_u8):
+    """a page as the caller gives it, numpy or torch -> the torch tensor of it, checked: ``[H, W, 3]`` uint8 with ``H, W >= 1``"""
+    t = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"page must be [H, W, 3] uint8, got {tuple(t.shape)} {t.dtype}")
+    return t
+
+
 def resize_page_u8(page_u8, size, device=None):
     """``[H, W, 3]`` uint8 -> ``[hs, ws, 3]`` uint8 for ``size = (hs, ws)``, equal byte for byte to
     ``PIL.Image.resize((ws, hs), Image.BICUBIC)``, computed on the device.  numpy or torch in, the same kind (and device) out; a host
     page is computed on ``device`` (default ``cuda:0``).  A side may change by a factor of 8 at the most, either way."""
-    t = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
-    if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
-        raise ValueError(f"page must be [H, W, 3] uint8, got {tuple(t.shape)} {t.dtype}")
+    t = _page_tensor(page_u8)
     hs, ws = int(size[0]), int(size[1])
     _check_resize(int(t.shape[0]), int(t.shape[1]), hs, ws)
     dev = torch.device(device) if device is not None else (t.device if t.is_cuda else torch.device("cuda:0"))
@@ -270,6 +276,36 @@ def _eval_mode(*nets):
     finally:
         for m, flag in saved:
             m.training = flag
+
+
+# The names ``TextEraser._mark`` is called with, in the order a page passes them (those of the stages that are off are left out, and of
+# each "a / b" pair the grid gives the first, ``pack``'s windows the second).  A mark closes the stage of its name, which began at the
+# mark before it: a stage's time on the stream is the time between those two.  Three marks close no stage: "start" (nothing is enqueued
+# yet), "joined" (the read-back tensor is formed; "counts_d2h" behind it is the copy alone) and "planned" (the host has selected the
+# tiles or planned the windows and uploaded their small index tensors).
+STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "hulls",
+               "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler",
+               "compose_page_u8", "compose_page_windows_u8", "download")
+
+
+@dataclass
+class PageState:
+    """One page between the three phases of ``TextEraser._erase``.  ``g`` / ``gs``: the page's grid and the segmenter's (the same
+    object without a working resolution); ``text``: the text plane on ``g``, ``text_s``: the segmenter's own (``text`` itself without a
+    working resolution); ``src``: the page the filler and compose see (``page_d``, or what the flat, smooth and tone stages painted);
+    ``both``: clean and mask in one buffer (one download), ``mask_u8`` its mask part; ``compose_mask``: the plane compose writes its
+    mask to (``mask_u8``, or scratch where a stage wrote the page's mask already); ``read_back``: the one tensor the synchronisation
+    copies."""
+    g: TileGrid
+    gs: TileGrid
+    page_d: torch.Tensor
+    text: torch.Tensor
+    text_s: torch.Tensor
+    src: torch.Tensor
+    both: torch.Tensor
+    mask_u8: torch.Tensor
+    compose_mask: torch.Tensor
+    read_back: torch.Tensor
 
 
 class TextEraser:
@@ -400,20 +436,23 @@ class TextEraser:
             p = next(segmenter.parameters(), None) if isinstance(segmenter, nn.Module) else None
             device = p.device if p is not None else torch.device("cuda:0")
         self.device = torch.device(device)
-        self.last_stats = None                          # {"tiles", "selected", "text_pixels"} of the latest page (+ "seg_tiles", "seg_size"; + "packed", "windows", "grid_selected"; + "flat_regions", "flat_pixels"; + "blocks"; + "smooth_regions", "smooth_pixels"; + "tone_regions", "tone_pixels")
-        self.last_regions = None                        # {"table", "found", "kept", "truncated"} of the latest page (regions path only; + "hull_area"; + "flat"; + "members", "components"; + "smooth"; + "tone")
+        self.last_stats = None                          # of the latest page: the ``last_stats`` keys of the class docstring
+        self.last_regions = None                        # its regions (regions path only): the ``last_regions`` keys of the class docstring
         self.last_labels = None                         # its int32 label plane, left on the device
-        self.last_route_labels = None                   # the int32 label plane the flat, smooth and tone stages worked on (``_route_labels``), left on the device; None unless one of them is enabled
+        self.last_route_labels = None                   # the int32 label plane the flat, smooth and tone stages worked on, left on the device; None unless one of them is enabled
 
-    # the stages, one method each so that tools/erase_bench.py can time them with events around the same code the call runs
+    # A page runs in three phases over one PageState: _enqueue, _read_back (the one synchronisation) and _finish with _download behind
+    # it (a method of its own: _erase puts the nets' flags back in front of it).  They call _mark at every boundary of STAGE_MARKS;
+    # tools/erase_bench.py replaces it by a recorder of events and so times the code the call runs.
+    def _mark(self, name):
+        """the page's course has reached the boundary ``name`` of ``STAGE_MARKS``: nothing to do"""
+
     def _upload(self, page):
-        t = torch.from_numpy(np.ascontiguousarray(page)) if isinstance(page, np.ndarray) else page
-        if t.dim() != 3 or t.shape[2] != 3 or t.dtype != torch.uint8 or t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError(f"page must be [H, W, 3] uint8, got {tuple(t.shape)} {t.dtype}")
-        return t.to(self.device).contiguous()
+        return _page_tensor(page).to(self.device).contiguous()
 
     def _segment(self, page_d, g):
         tiles = _page_tiles_norm(page_d, g, self.scale, self.shift)
+        self._mark("page_tiles_norm")
         x = tiles.permute(0, 3, 1, 2)                   # [N,3,T,T] view in channels-last memory: to_nhwc() inside the nets is free
         logits = None
         for b0 in range(0, g.count, self.tile_batch):
@@ -430,77 +469,23 @@ class TextEraser:
                 logits[b0:b0 + n].copy_(lb)             # bf16 logits (bf16 activation storage) are cast here, once
         return logits
 
-    def _regions(self, text, g):
-        """filter the text plane in place -> ONE device tensor [filtered core counts | found, kept | table]; the labels stay on the device.
-        With ``group`` the blocks stage filters: every region is labelled and no table is made here."""
-        if self.group is not None:
-            self.last_labels, packed = _text_regions(text, self.connectivity, 0, 0, g)
-            return packed
-        self.last_labels, packed = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=self._tail())
-        return packed
+    def _layout(self, g):
+        """the page's read-back tensor: what rides where in it"""
+        return ReadBack(g.count, self.max_regions, self.hull, self.group is not None, self.flat is not None, self.smooth is not None,
+                        self.tone is not None, regions=self.regions)
 
-    def _layout(self, nt=0):
-        """where the rows of the enabled ones of the flat, smooth and tone stages ride behind the table of the labelling they work on
-        (``nt``: the core counts in front of it); tools/erase_bench.py unpacks its read-back with it"""
-        return RouteLayout(nt, self.max_regions, self.flat is not None, self.smooth is not None, self.tone is not None)
-
-    def _tail(self):
-        """the words behind the table that the stage behind it writes"""
-        return self.max_regions if self.hull else self._layout().tail
-
-    def _blocks(self, text, g, packed):
-        """group the labelled regions into blocks and filter those, in place -> (the blocks' [core counts | found, kept | table], in the
-        layout ``_regions`` gives the regions' own, and the tensor it is the front of: members and the component count ride behind it);
-        ``last_labels`` becomes the block-label plane"""
-        self.last_labels, packed, whole = _text_blocks(text, self.last_labels, packed[g.count:g.count + 2], self.group, self.min_area,
-                                                       self.max_regions, g, tail=self._tail())
-        return packed, whole
-
-    def _hulls(self, text, g, packed):
-        """fill the kept regions' hulls into the text plane in place; packed becomes [core counts of the filled plane | ... | hull_area]"""
-        _region_hulls(text, self.last_labels, packed, self.max_regions, g)
-        return packed
-
-    def _route_labels(self, text, g, packed):
-        """what the flat, smooth and tone stages work on -> (labels, ONE device tensor ``[core counts | found, kept | table | flat rows |
-        smooth rows | tone rows]``, the number of words of ``packed`` that ride in front of it in the read-back).  Behind the hulls the filled plane is
-        labelled once more, for both stages (hull pixels carry no label), and that call's tensor rides behind ``packed``; otherwise the
-        rows are the tail of ``packed`` itself and nothing rides in front."""
-        if self.hull:
-            labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=self._layout().tail)
-            return labels, own, int(packed.numel())
-        return self.last_labels, packed, 0
-
-    def _flat(self, page_d, text, g, route, mask_u8):
-        """paint the flat regions and take them out of the text plane in place -> the painted page; ``mask_u8`` gets the mask of the whole
-        plane.  ``route``: ``_route_labels``' triple; the core counts of the reduced plane are at the front of its tensor."""
-        labels, own, _ = route
-        lay = self._layout(g.count)
-        painted = torch.empty_like(page_d)
-        _flat_regions(page_d, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows("flat")], self.max_regions, self.flat_ring, self.flat,
-                      painted, mask_u8, g, own[lay.counts])
-        return painted
-
-    def _smooth(self, src, text, g, route, mask_u8):
-        """fill the smooth regions harmonically and take them out of the text plane in place -> the filled page (a new buffer; ``src``:
-        the page, or the flat stage's).  ``mask_u8``: the plane that gets the mask of the whole plane on entry, None where the flat stage
-        wrote the page's already.  The core counts at the front of ``route``'s tensor are rewritten for the reduced plane."""
-        labels, own, _ = route
-        lay = self._layout(g.count)
+    def _route(self, name, src, text, g, labels, own, mask_u8):
+        """the flat, smooth or tone stage: fill the regions it takes and take them out of the text plane in place -> the filled page (a new
+        buffer; ``src``: the page, or the stage's before).  ``labels`` and ``own``: the labelling the stages work on and its tensor,
+        ``[core counts | found, kept | table | the stages' rows]``, whose core counts are rewritten for the reduced plane.  ``mask_u8``: the
+        plane that gets the mask of the whole plane on entry, None where an earlier stage wrote the page's already."""
+        run, scalars = {"flat": (_flat_regions, (self.flat_ring, self.flat)),
+                        "smooth": (_smooth_regions, (self.smooth_ring, self.smooth, self.smooth_sweeps)),
+                        "tone": (_tone_regions, (self.tone_ring, self.tone_period, self.tone))}[name]
+        lay = self._layout(g).routes
         painted = torch.empty_like(src)
-        _smooth_regions(src, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows("smooth")], self.max_regions, self.smooth_ring,
-                        self.smooth, self.smooth_sweeps, painted, mask_u8, g, own[lay.counts])
-        return painted
-
-    def _tone(self, src, text, g, route, mask_u8):
-        """fill the tone regions from one period away and take them out of the text plane in place -> the filled page (a new buffer;
-        ``src``: the page, or the stage's before).  ``mask_u8``: the plane that gets the mask of the whole plane on entry, None where an
-        earlier stage wrote the page's already.  The core counts at the front of ``route``'s tensor are rewritten for the reduced plane."""
-        labels, own, _ = route
-        lay = self._layout(g.count)
-        painted = torch.empty_like(src)
-        _tone_regions(src, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows("tone")], self.max_regions, self.tone_ring,
-                      self.tone_period, self.tone, painted, mask_u8, g, own[lay.counts])
+        run(src, text, labels, own[lay.table], own[lay.n_regions], own[lay.rows(name)], self.max_regions, *scalars, painted, mask_u8, g,
+            own[lay.counts])
         return painted
 
     def _run_filler(self, img, mplane, g):
@@ -520,14 +505,6 @@ class TextEraser:
                 out[b0:b0 + n].copy_(ob.permute(0, 2, 3, 1))
         return out
 
-    def _fill(self, page_d, text, g, selected):
-        ids = torch.tensor(selected, dtype=torch.int32).to(self.device)
-        slot_h = np.full(g.count, -1, np.int32)
-        slot_h[selected] = np.arange(len(selected), dtype=np.int32)
-        slot = torch.from_numpy(slot_h).to(self.device)
-        img, mplane = _page_tiles_fill(page_d, text, g, ids)
-        return self._run_filler(img, mplane, g), slot
-
     def _plan(self, table, truncated, g, n_grid):
         """the windows to use instead of the grid's ``n_grid`` tiles -> (origins, rects) on the host, or None: stay on the grid"""
         if truncated or n_grid < 2:                     # regions beyond the table have no box; one tile cannot become fewer
@@ -535,96 +512,130 @@ class TextEraser:
         origins, rects = plan_fill_windows(table[:, 2:6], g.h, g.w, g.tile, g.halo)
         return (origins, rects) if 0 < len(origins) <= MAX_FILL_WINDOWS and len(origins) < n_grid else None
 
-    def _fill_windows(self, page_d, text, g, origins, rects):
-        origin, rect = torch.from_numpy(origins).to(self.device), torch.from_numpy(rects).to(self.device)
-        img, mplane = _page_windows_fill(page_d, text, g, origin)
-        return self._run_filler(img, mplane, g), origin, rect
-
-    def _erase(self, page):
-        page_d = self._upload(page)
+    def _enqueue(self, page) -> PageState:
+        """phase 1: everything up to the one tensor the synchronisation copies, on the stream"""
+        self._mark("start")
+        page_d = seg_page = self._upload(page)
+        self._mark("upload")
         h, w = int(page_d.shape[0]), int(page_d.shape[1])
-        g = gs = tile_grid(h, w, self.tile, self.halo)  # gs: the grid the segmenter works on
+        g = gs = tile_grid(h, w, self.tile, self.halo)
         if self.seg_long_side is not None:
             hs, ws = working_size(h, w, self.seg_long_side)
             _check_resize(h, w, hs, ws)
             if (hs, ws) != (h, w):
                 gs = tile_grid(hs, ws, self.tile, self.halo)
-        with torch.no_grad(), _eval_mode(self.segmenter, self.filler):
-            logits = self._segment(page_d if gs is g else _page_resize_u8(page_d, gs.h, gs.w), gs)
-            text, counts = _tiles_text_mask(logits, gs, self.logit_threshold, self.dilate)
-            if gs is not g:
-                text, counts = _text_plane_up(text, g)
-            off = (h * w * 3 + 15) // 16 * 16           # clean + mask in one buffer (one download); the kernels want both 4-byte aligned
-            both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
-            clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
-            src, compose_mask, split = page_d, mask_u8, 0   # src: the page the filler and compose see
-            if self.regions:
-                counts = self._regions(text, g)
-                if self.group is not None:
-                    counts, whole = blocks = self._blocks(text, g, counts)
-                if self.hull:
-                    counts = self._hulls(text, g, counts)
-                if self.routes:
-                    route = self._route_labels(text, g, counts)
-                    self.last_route_labels = route[0]
-                    stages = [(self.flat, self._flat), (self.smooth, self._smooth), (self.tone, self._tone)]
-                    for k, stage in enumerate(run for on, run in stages if on is not None):     # each works on the page the one before left
-                        src = stage(src, text, g, route, None if k else mask_u8)
-                    compose_mask = torch.empty_like(mask_u8)        # the first enabled stage wrote the page's mask (later ones get None);
-                                                                    # compose's, of the reduced plane, is scratch
-                    split = route[2]
-                    counts = torch.cat([counts, route[1]]) if split else route[1]
-                if self.group is not None:              # members and the component count: the last words of the read-back
-                    ride = int(blocks[0].numel())
-                    counts = whole if counts is blocks[0] else torch.cat([counts, whole[ride:]])
-            counts_h = all_h = counts.cpu().numpy()     # the one synchronisation before the download
-            route_stats = {}                            # "flat_regions", "flat_pixels", ... of the enabled stages
-            if self.regions:
-                if self.group is not None:
-                    all_h, blocks_h = all_h[:-(self.max_regions + 1)], all_h[-(self.max_regions + 1):]
-                packed_h = all_h[:split] if split else all_h
-                counts_h, table, found, kept, truncated = unpack_regions(packed_h, g.count, self.max_regions)
-                self.last_regions = {"table": table, "found": found, "kept": kept, "truncated": truncated}
-                if self.group is not None:
-                    members, components = unpack_blocks(blocks_h, 0, self.max_regions, len(table))
-                    self.last_regions.update(members=members, components=components)
-                if self.hull:
-                    self.last_regions["hull_area"] = unpack_hull_area(packed_h, g.count, self.max_regions, len(table))
-                if self.routes:                         # behind the hulls: the filled plane's own components; all that follows works on them
-                    counts_h, ftable, truncated, stages, gone = unpack_routes(all_h[split:], self._layout(g.count))
-                    self.last_regions.update(stages)
-                    for name, stage in stages.items():
-                        route_stats[name + "_regions"] = int(stage["is_" + name].sum())
-                        route_stats[name + "_pixels"] = int(ftable[stage["is_" + name], 1].sum(dtype=np.int64))
-                    table = ftable[~gone]               # what pack plans its windows on
-            selected = [t for t in range(g.count) if counts_h[t] > 0 or not self.skip_blank_tiles]
-            any_text = bool(counts_h.sum() > 0)
-            windows = self._plan(table, truncated, g, len(selected)) if (self.pack and any_text) else None
-            if windows is not None:
-                out, origin, rect = self._fill_windows(src, text, g, *windows)
-            else:
-                out, slot = self._fill(src, text, g, selected) if (selected and any_text) else (None, None)
-            if windows is not None:
-                _compose_page_windows_u8(src, text, out, origin, rect, g, clean, compose_mask)
-            else:
-                _compose_page_u8(src, text, out, slot, g, clean, compose_mask)
+                seg_page = _page_resize_u8(page_d, hs, ws)
+                self._mark("resize")
+        logits = self._segment(seg_page, gs)
+        self._mark("segmenter")
+        text, counts = _tiles_text_mask(logits, gs, self.logit_threshold, self.dilate)
+        self._mark("tiles_text_mask")
+        text_s = text
+        if gs is not g:
+            text, counts = _text_plane_up(text_s, g)
+            self._mark("plane_up")
+        off = (h * w * 3 + 15) // 16 * 16               # clean + mask in one buffer (one download); the kernels want both 4-byte aligned
+        both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
+        mask_u8 = both[off:].view(h, w)
+        st = PageState(g, gs, page_d, text, text_s, page_d, both, mask_u8, mask_u8, counts)
+        if self.regions:
+            self._enqueue_regions(st)
+        self._mark("joined")
+        return st
+
+    def _enqueue_regions(self, st):
+        """the regions path of phase 1, in place on ``st.text``: labelling, blocks, hulls and the flat, smooth and tone stages"""
+        g, text, lay = st.g, st.text, self._layout(st.g)
+        second = whole = None
+        if self.group is None:
+            self.last_labels, first = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=lay.tail)
+            self._mark("regions")
+        else:                                           # every region is labelled and no table is made: the blocks stage filters
+            labels, every = _text_regions(text, self.connectivity, 0, 0, g)
+            self._mark("regions")
+            self.last_labels, first, whole = _text_blocks(text, labels, every[lay.n_regions], self.group, self.min_area, self.max_regions, g,
+                                                          tail=lay.tail)
+            self._mark("blocks")
+        if self.hull:
+            _region_hulls(text, self.last_labels, first, self.max_regions, g)
+            self._mark("hulls")
+        if self.routes:
+            labels, own = self.last_labels, first
+            if self.hull:                               # hull pixels carry no label: the filled plane is labelled once more, for all stages
+                labels, own = _text_regions(text, self.connectivity, 0, self.max_regions, g, tail=lay.second_tail)
+                second = own
+            self.last_route_labels = labels
+            for k, name in enumerate(lay.routes.stages):        # each works on the page the one before left
+                st.src = self._route(name, st.src, text, g, labels, own, None if k else st.mask_u8)
+                self._mark(name)
+            st.compose_mask = torch.empty_like(st.mask_u8)      # the first stage wrote the page's mask; compose's, of the reduced plane, is scratch
+        st.read_back = lay.join(first, second, whole)
+
+    def _read_back(self, st):
+        """phase 2: the one synchronisation before the download -> ``regions.PageRead``"""
+        host = st.read_back.cpu().numpy()
+        self._mark("counts_d2h")
+        read = self._layout(st.g).unpack(host)
+        if self.regions:
+            named = ("table", "found", "kept", "truncated", "members", "components", "hull_area")
+            self.last_regions = {k: getattr(read, k) for k in named if getattr(read, k) is not None}
+            self.last_regions.update(read.stages)
+        return read
+
+    def _finish(self, st, read):
+        """phase 3, up to its download (``_download``): select or plan, fill, compose into ``st.both``; ``last_stats``"""
+        g, h, w = st.g, st.g.h, st.g.w
+        selected = [t for t in range(g.count) if read.counts[t] > 0 or not self.skip_blank_tiles]
+        any_text = bool(read.counts.sum() > 0)
+        windows = self._plan(read.plan_table, read.plan_truncated, g, len(selected)) if (self.pack and any_text) else None
+        where = None                                    # on the device: (origin, rect) of the windows, or (ids, slot) of the grid's tiles
+        if windows is not None:
+            where = [torch.from_numpy(a).to(self.device) for a in windows]
+        elif selected and any_text:
+            slot_h = np.full(g.count, -1, np.int32)
+            slot_h[selected] = np.arange(len(selected), dtype=np.int32)
+            where = [torch.tensor(selected, dtype=torch.int32).to(self.device), torch.from_numpy(slot_h).to(self.device)]
+        self._mark("planned")
+        out = None
+        if where is not None:
+            img, mplane = (_page_tiles_fill if windows is None else _page_windows_fill)(st.src, st.text, g, where[0])
+        self._mark("page_tiles_fill" if windows is None else "page_windows_fill")
+        if where is not None:
+            out = self._run_filler(img, mplane, g)
+        self._mark("filler")
+        clean = st.both[:h * w * 3].view(h, w, 3)
+        if windows is None:
+            _compose_page_u8(st.src, st.text, out, None if where is None else where[1], g, clean, st.compose_mask)
+        else:
+            _compose_page_windows_u8(st.src, st.text, out, *where, g, clean, st.compose_mask)
+        self._mark("compose_page_u8" if windows is None else "compose_page_windows_u8")
+        route_stats = {}                                # "flat_regions", "flat_pixels", ... of the enabled stages
+        for name, stage in read.stages.items():
+            route_stats[name + "_regions"] = int(stage["is_" + name].sum())
+            route_stats[name + "_pixels"] = int(read.route_table[stage["is_" + name], 1].sum(dtype=np.int64))
         self.last_stats = {"tiles": g.count, "selected": int(out.shape[0]) if out is not None else 0,
-                           "text_pixels": int(counts_h.sum()) + sum(v for k, v in route_stats.items() if k.endswith("_pixels"))}
+                           "text_pixels": int(read.counts.sum()) + sum(v for k, v in route_stats.items() if k.endswith("_pixels"))}
         if self.group is not None:
-            self.last_stats.update(blocks=self.last_regions["kept"])
+            self.last_stats.update(blocks=read.kept)
         self.last_stats.update(route_stats)
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)
         if self.seg_long_side is not None:
-            self.last_stats.update(seg_tiles=gs.count, seg_size=(gs.h, gs.w))
-        if isinstance(page, np.ndarray):
-            both_h = both.cpu().numpy()
-            return both_h[:h * w * 3].reshape(h, w, 3), both_h[off:].reshape(h, w)
-        if page.device != self.device:
-            both = both.to(page.device)
-            clean, mask_u8 = both[:h * w * 3].view(h, w, 3), both[off:].view(h, w)
-        return clean, mask_u8
+            self.last_stats.update(seg_tiles=st.gs.count, seg_size=(st.gs.h, st.gs.w))
+
+    def _download(self, st, page):
+        """the end of phase 3: the one download -> (clean, mask) of the kind of ``page``, on its device"""
+        h, w = st.g.h, st.g.w
+        both = st.both.cpu().numpy() if isinstance(page, np.ndarray) else st.both.to(page.device)
+        self._mark("download")
+        return both[:h * w * 3].reshape(h, w, 3), both[both.shape[0] - h * w:].reshape(h, w)
+
+    def _erase(self, page):
+        with torch.no_grad(), _eval_mode(self.segmenter, self.filler):
+            st = self._enqueue(page)
+            self._finish(st, self._read_back(st))
+        return self._download(st, page)                 # behind the with: the nets' flags are put back while the device still works
 
     def __call__(self, page):
         if isinstance(page, (list, tuple)):

@@ -172,6 +172,73 @@ class RouteLayout:
         return self._rows[name]
 
 
+class PageRead(NamedTuple):
+    """What ``ReadBack.unpack`` finds in the host copy.  ``counts``: the core counts that select tiles (of the plane the last stage
+    left).  ``table`` / ``found`` / ``kept`` / ``truncated``: the first labelling's (with ``group``: the blocks').  ``hull_area``,
+    ``members`` / ``components``: with ``hull`` / ``group``, else None.  ``route_table`` (the components the flat, smooth and tone stages
+    worked on), ``stages`` and ``gone`` as ``unpack_routes`` gives them: None, {} and None without such a stage.  ``plan_table`` /
+    ``plan_truncated``: the regions that still hold text, for ``plan_fill_windows``.  Without the regions path all but ``counts`` is None."""
+    counts: np.ndarray
+    table: np.ndarray = None
+    found: int = None
+    kept: int = None
+    truncated: bool = None
+    hull_area: np.ndarray = None
+    members: np.ndarray = None
+    components: int = None
+    route_table: np.ndarray = None
+    stages: dict = None
+    gone: np.ndarray = None
+    plan_table: np.ndarray = None
+    plan_truncated: bool = None
+
+
+class ReadBack:
+    """The ONE int32 tensor a page's only synchronisation copies, and the only place that knows its offsets: ``[first | second | members
+    (max_regions), components]``.  ``first`` is the first labelling's tensor, ``[core counts (nt) | found, kept | table | tail]`` -- the
+    blocks' with ``group`` -- whose ``tail`` words are the hull areas with ``hull``, else the route rows (``RouteLayout``).  ``second`` is
+    there with ``hull`` and a route stage: the tensor of the labelling of the filled plane, in ``RouteLayout``'s form (``second_tail``
+    words behind its table).  The last part is there with ``group``.  ``routes`` is the ``RouteLayout`` of the tensor the route stages
+    work on, the second where there is one, else the first.  Without ``regions`` the tensor is the ``nt`` core counts alone."""
+
+    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True):
+        n = int(max_regions)
+        self.routes = RouteLayout(nt, n, flat, smooth, tone)
+        self.regions, self.hull, self.group = bool(regions), bool(hull), bool(group)
+        self.n_regions, self.second_tail = self.routes.n_regions, self.routes.tail
+        self.tail = n if self.hull else self.routes.tail
+        self.first = slice(0, self.routes.table.stop + self.tail)
+        self.hull_area = slice(self.routes.table.stop, self.first.stop)
+        two = self.hull and bool(self.routes.stages)
+        self.own = slice(self.first.stop, self.first.stop + self.routes.words) if two else self.first
+        self.members = slice(self.own.stop, self.own.stop + n)
+        self.words = self.members.stop + 1 if self.group else self.own.stop if self.regions else int(nt)
+
+    def join(self, first, second=None, whole=None):
+        """the tensor to copy, from what the stages left on the device: ``first``, ``second`` (None where the route stages worked on
+        ``first``) and, with ``group``, ``whole``: ``_text_blocks``' tensor, whose front ``first`` is.  Copies only where a tensor has to
+        ride between ``first`` and the members."""
+        if second is None:
+            return first if whole is None else whole
+        return torch.cat([first, second] if whole is None else [first, second, whole[self.first.stop:]])
+
+    def unpack(self, host) -> PageRead:
+        """the host copy of the joined tensor -> ``PageRead``; ``host`` is not written, the tables and columns are copies"""
+        if not self.regions:
+            return PageRead(host, stages={})
+        counts, table, found, kept, truncated = unpack_regions(host[self.first], self.routes.nt, self.routes.max_regions)
+        n = len(table)
+        read = PageRead(counts, table, found, kept, truncated, stages={}, plan_table=table, plan_truncated=truncated)
+        if self.hull:
+            read = read._replace(hull_area=host[self.hull_area][:n].copy())
+        if self.group:
+            read = read._replace(members=host[self.members][:n].copy(), components=int(host[self.members.stop]))
+        if self.routes.stages:                          # behind the hulls: the filled plane's own components; all that follows works on them
+            counts, rtable, rtruncated, stages, gone = unpack_routes(host[self.own], self.routes)
+            read = read._replace(counts=counts, route_table=rtable, stages=stages, gone=gone, plan_table=rtable[~gone], plan_truncated=rtruncated)
+        return read
+
+
 def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
     """``tsii_text_regions`` in place on the device plane ``text`` -> (labels, packed): ``packed`` is ONE int32 device tensor
     ``[core counts (grid.count, with a grid) | found, kept | table rows | tail words]``, so that a caller reads everything back with
@@ -214,11 +281,6 @@ def _text_blocks(text, labels, counts, gap, min_area, max_regions, grid=None, ta
     call("tsii_text_blocks", ptr(text), ptr(labels), h, w, int(gap), int(min_area), n, tile, halo, ptr(whole[:nt]) if nt else None,
          ptr(block_labels), ptr(whole[nt + 2:]), ptr(whole[front:]), ptr(whole[nt:nt + 2]), ptr(ws), _lib.stream())
     return block_labels, whole[:front], whole
-
-
-def unpack_blocks(whole_h, front, max_regions, n):
-    """host copy of ``whole`` (``front``: the words of its ``packed`` part) -> (members of the ``n`` table rows in use, components)"""
-    return whole_h[front:front + n].copy(), int(whole_h[front + int(max_regions)])
 
 
 def _region_hulls(text, labels, packed, max_regions, grid=None):
@@ -338,12 +400,6 @@ def unpack_routes(own_h, layout):
     return counts_h, table, truncated, stages, gone
 
 
-def unpack_hull_area(packed_h, nt, max_regions, n):
-    """host copy of the grown ``packed`` -> hull_area of the ``n`` table rows in use"""
-    at = nt + 2 + 6 * int(max_regions)
-    return packed_h[at:at + n].copy()
-
-
 def unpack_regions(packed_h, nt, max_regions):
     """host copy of ``packed`` -> (core counts, table, found, kept, truncated)"""
     found, kept = int(packed_h[nt]), int(packed_h[nt + 1])
@@ -374,12 +430,11 @@ def fill_region_hulls(text, connectivity=8, min_area=0, max_regions=4096, device
     which is not modified; one synchronisation (the read-back of the counts, the table and the hull areas)."""
     check_region_args(connectivity, min_area, max_regions)
     plane = _plane_on_device(text, device)
-    labels, packed = _text_regions(plane, connectivity, min_area, max_regions, tail=int(max_regions))
+    rb = ReadBack(0, max_regions, hull=True)
+    labels, packed = _text_regions(plane, connectivity, min_area, max_regions, tail=rb.tail)
     _region_hulls(plane, labels, packed, max_regions)
-    packed_h = packed.cpu().numpy()
-    _, table, found, kept, truncated = unpack_regions(packed_h, 0, max_regions)
-    hull_area = unpack_hull_area(packed_h, 0, max_regions, len(table))
-    return RegionHulls(_like(plane * 255, text), TextRegions(_like(labels, text), table, found, kept, truncated), hull_area)
+    r = rb.unpack(packed.cpu().numpy())
+    return RegionHulls(_like(plane * 255, text), TextRegions(_like(labels, text), r.table, r.found, r.kept, r.truncated), r.hull_area)
 
 
 def _page_and_plane(page_u8, mask_u8, device):
@@ -475,11 +530,9 @@ def text_blocks(mask_u8, gap, connectivity=8, min_area=0, max_regions=4096, devi
     check_block_args(gap)
     plane = _plane_on_device(mask_u8, device)
     labels, counts = _text_regions(plane, connectivity, 0, 0)
-    block_labels, packed, whole = _text_blocks(plane, labels, counts, gap, min_area, max_regions)
-    whole_h = whole.cpu().numpy()
-    _, table, found, kept, _ = unpack_regions(whole_h, 0, max_regions)
-    members, components = unpack_blocks(whole_h, int(packed.numel()), max_regions, len(table))
-    return TextBlocks(_like(plane * 255, mask_u8), _like(block_labels, mask_u8), table, members, found, kept, components)
+    block_labels, _, whole = _text_blocks(plane, labels, counts, gap, min_area, max_regions)
+    r = ReadBack(0, max_regions, group=True).unpack(whole.cpu().numpy())
+    return TextBlocks(_like(plane * 255, mask_u8), _like(block_labels, mask_u8), r.table, r.members, r.found, r.kept, r.components)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

@@ -6,7 +6,13 @@
                                 [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T] [--tones SHARE] [--tone T [--tone-ring N] [--tone-period N]]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
-tsii_compose_page_u8, download.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
+tsii_compose_page_u8, download.  The tool has no copy of the page's course: it puts a recorder in the place of ``TextEraser._mark``
+(one HIP event per mark) and runs the eraser's own phases, ``_enqueue``, ``_read_back``, ``_finish`` and ``_download``; a stage's time
+is the time between the mark that closes it and the mark before (``pipeline.STAGE_MARKS``).  So every stage is the code the call runs,
+on the buffers the call uses: the ``segmenter`` stage includes the gather of the batches' logits, the ``filler`` stage is
+``TextEraser._run_filler`` (the gather into one buffer instead of a list and ``torch.cat``), compose writes into the joint clean + mask
+buffer and ``download`` is its one copy.  ``_segment`` is wrapped to put the synthetic logits in the net's place, ``_plan`` to time it
+with the host clock.  Each kernel's bytes come from the accounting in DESIGN.md ("page pipeline"), computed here from
 the shapes.  Random-init weights put no meaningful text on a page, so the segmenter's logits are timed as they are and then
 REPLACED by a synthetic logit field (rectangular text blobs over ``--text-fraction`` of the page) for the stages behind it: what is
 timed is the cost of the pipeline, not the quality of a net.  For comparison, in the same run:
@@ -192,157 +198,50 @@ def main(argv=None):
         return er
     eraser = make(True)
 
-    ev = lambda: torch.cuda.Event(enable_timing=True)
-    stages = ["upload", "page_tiles_norm", "segmenter", "tiles_text_mask", "counts_d2h", "page_tiles_fill", "filler", "compose_page_u8", "download"]
-    if with_regions:
-        stages.append("regions")                            # timed with its own pair of events, between the mask and the read-back
-    if with_blocks:
-        stages.append("blocks")                             # its own pair of events, right behind the regions stage
-    if args.hull:
-        stages.append("hulls")                              # its own pair of events, right behind the regions (or blocks) stage
-    if with_flat:
-        stages.append("flat")                               # its own pair of events, behind the regions / hulls stages
-    if with_smooth:
-        stages.append("smooth")                             # its own pair of events, behind the flat stage
-    if with_tone:
-        stages.append("tone")                               # its own pair of events, behind the smooth stage
-    if with_seg:
-        stages += ["resize", "plane_up"]                    # their own pairs of events: behind the upload / behind the mask
+    class Recorder:
+        """``TextEraser._mark`` as a recorder: one HIP event per mark, on the current stream"""
+        def __init__(self):
+            self.names, self.events = [], []
+
+        def __call__(self, name):
+            self.names.append(name)
+            self.events.append(torch.cuda.Event(enable_timing=True))
+            self.events[-1].record()
+
+        def stage_ms(self):
+            """every mark but the first: the time from the mark before it (pipeline.STAGE_MARKS: the stage it closes)"""
+            return {name: self.events[i].elapsed_time(self.events[i + 1]) for i, name in enumerate(self.names[1:])}
+
+    planned, plan = {}, eraser._plan
+
+    def timed_plan(*a):                                     # host clock: behind the read-back nothing else is in flight
+        t0 = time.perf_counter()
+        planned["windows"] = plan(*a)
+        planned["ms"] = (time.perf_counter() - t0) * 1e3
+        return planned["windows"]
+    eraser._plan = timed_plan
 
     def one_page():
-        marks = [ev() for _ in range(11)]
-        reg0, reg1, hul1, res1, up0, up1, fl0, fl1, blk1, sm0, sm1, tn0, tn1 = (ev() for _ in range(13))
-        page_pinned = torch.from_numpy(page)
-        with torch.no_grad():
-            marks[0].record()
-            page_d = page_pinned.to(dev)
-            marks[1].record()
-            seg_page = page_d
-            if with_seg:
-                seg_page = P._page_resize_u8(page_d, hs, ws)
-                res1.record()
-            tiles = P._page_tiles_norm(seg_page, gs, eraser.scale, eraser.shift)
-            marks[2].record()
-            x = tiles.permute(0, 3, 1, 2)
-            for b in range(0, gs.count, args.tile_batch):
-                seg(x[b:b + args.tile_batch])
-            marks[3].record()
-            text, counts = P._tiles_text_mask(logits_fixed, gs, eraser.logit_threshold, args.dilate)
-            text_s = text
-            if with_seg:
-                up0.record()
-                text, counts = P._text_plane_up(text, g)
-                up1.record()
-            if with_regions:
-                reg0.record()
-                counts = eraser._regions(text, g)           # tsii_text_regions; the labels stay in eraser.last_labels
-                reg1.record()
-                if with_blocks:
-                    counts, whole = blocks = eraser._blocks(text, g, counts)     # tsii_text_blocks; last_labels becomes the block labels
-                    blk1.record()
-                if args.hull:
-                    counts = eraser._hulls(text, g, counts)
-                    hul1.record()
-            src, split = page_d, 0                          # src: the page the filler and compose see
-            if with_routes:                                 # the second labelling behind the hulls is timed with the first stage that needs it
-                page_mask = torch.empty((h, w), dtype=torch.uint8, device=dev)
-                (fl0 if with_flat else sm0 if with_smooth else tn0).record()
-                route = eraser._route_labels(text, g, counts)
-                if with_flat:
-                    src = eraser._flat(page_d, text, g, route, page_mask)
-                    fl1.record()
-                    sm0.record()
-                if with_smooth:
-                    src = eraser._smooth(src, text, g, route, None if with_flat else page_mask)
-                    sm1.record()
-                if with_tone:
-                    if with_flat or with_smooth:
-                        tn0.record()
-                    src = eraser._tone(src, text, g, route, None if (with_flat or with_smooth) else page_mask)
-                    tn1.record()
-                split = route[2]
-                counts = torch.cat([counts, route[1]]) if split else route[1]
-            if with_blocks:                                 # members and the component count ride at the end, as in the eraser
-                counts = whole if counts is blocks[0] else torch.cat([counts, whole[int(blocks[0].numel()):]])
-            marks[4].record()
-            counts_h = counts.cpu().numpy()                 # the one read-back: counts (+ region counts + table + flat rows + members)
-            marks[5].record()
-            d2h_words = int(counts_h.size)
-            region_info = None
-            if with_regions:
-                packed_h = counts_h
-                if with_blocks:
-                    packed_h, blocks_h = counts_h[:-(args.max_regions + 1)], counts_h[-(args.max_regions + 1):]
-                counts_h, table, found, kept, truncated = RG.unpack_regions(packed_h, g.count, args.max_regions)
-                region_info = {"found": found, "kept": kept, "truncated": truncated}
-                if with_blocks:
-                    members, components = RG.unpack_blocks(blocks_h, 0, args.max_regions, len(table))
-                    region_info.update(components=components, largest_block=int(members.max()) if len(members) else 0)
-                if args.hull:
-                    region_info["hull_pixels"] = int(RG.unpack_hull_area(packed_h[:split] if split else packed_h, g.count, args.max_regions,
-                                                                         len(table)).sum(dtype=np.int64))
-                if with_routes:                             # everything behind works on these stages' own components and counts
-                    counts_h, ftable, truncated, route_stages, gone = RG.unpack_routes(packed_h[split:], eraser._layout(g.count))
-                    region_info.update(labelled=len(ftable))
-                    for name, stage in route_stages.items():
-                        is_ = stage["is_" + name]
-                        region_info.update({name + "_regions": int(is_.sum()), name + "_pixels": int(ftable[is_, 1].sum(dtype=np.int64))})
-                    table = ftable[~gone]
-            selected = [t for t in range(g.count) if counts_h[t] > 0]
-            windows, plan_ms = None, 0.0
-            if args.pack:
-                t0 = time.perf_counter()
-                windows = eraser._plan(table, truncated, g, len(selected))
-                plan_ms = (time.perf_counter() - t0) * 1e3
-            if windows is not None:
-                origin, rect = torch.from_numpy(windows[0]).to(dev), torch.from_numpy(windows[1]).to(dev)
-                n_fill = len(windows[0])
-            else:
-                ids = torch.tensor(selected, dtype=torch.int32).to(dev)
-                slot_h = np.full(g.count, -1, np.int32)
-                slot_h[selected] = np.arange(len(selected), dtype=np.int32)
-                slot = torch.from_numpy(slot_h).to(dev)
-                n_fill = len(selected)
-            marks[10].record()                              # the two small uploads above belong to no stage
-            if n_fill:
-                img, mplane = P._page_windows_fill(src, text, g, origin) if windows is not None else P._page_tiles_fill(src, text, g, ids)
-            marks[6].record()
-            out = None                                      # a page whose text is all flat: the filler is not called
-            if n_fill:
-                xi = img.permute(0, 3, 1, 2)
-                outs = [P.to_nhwc(fil((xi[b:b + args.tile_batch], P.MaskParts.from_plane(mplane[b:b + args.tile_batch], 3))))
-                        for b in range(0, n_fill, args.tile_batch)]
-                out = outs[0] if len(outs) == 1 else torch.cat(outs)
-            marks[7].record()
-            clean, mask_u8 = torch.empty((h, w, 3), dtype=torch.uint8, device=dev), torch.empty((h, w), dtype=torch.uint8, device=dev)
-            if windows is not None:
-                P._compose_page_windows_u8(src, text, out, origin, rect, g, clean, mask_u8)
-            else:
-                P._compose_page_u8(src, text, out, slot if out is not None else None, g, clean, mask_u8)
-            marks[8].record()
-            clean.cpu(), mask_u8.cpu()
-            marks[9].record()
+        rec = eraser._mark = Recorder()
+        planned.update(windows=None, ms=0.0)
+        with torch.no_grad():                               # the nets are in eval() mode already
+            st = eraser._enqueue(page)
+            read = eraser._read_back(st)                    # the one read-back: counts (+ region counts + table + flat rows + members)
+            eraser._finish(st, read)
+            eraser._download(st, page)
         torch.cuda.synchronize()
-        t = [marks[i].elapsed_time(marks[i + 1]) for i in range(9)]
-        t[5] = marks[10].elapsed_time(marks[6])
+        stats, region_info = eraser.last_stats, None
         if with_regions:
-            t[3] = marks[3].elapsed_time(reg0)
-            t.append(reg0.elapsed_time(reg1))
-        if with_blocks:
-            t.append(reg1.elapsed_time(blk1))
-        if args.hull:
-            t.append((blk1 if with_blocks else reg1).elapsed_time(hul1))
-        if with_flat:
-            t.append(fl0.elapsed_time(fl1))
-        if with_smooth:
-            t.append(sm0.elapsed_time(sm1))
-        if with_tone:
-            t.append(tn0.elapsed_time(tn1))
-        if with_seg:
-            t[1] = res1.elapsed_time(marks[2])
-            t[3] = marks[3].elapsed_time(up0)
-            t += [marks[1].elapsed_time(res1), up0.elapsed_time(up1)]
-        return t, len(selected), int(counts_h.sum()), (page_d, text, out, tiles, text_s), d2h_words, region_info, windows, plan_ms
+            region_info = {"found": read.found, "kept": read.kept, "truncated": read.truncated}
+            if with_blocks:
+                region_info.update(components=read.components, largest_block=int(read.members.max()) if len(read.members) else 0)
+            if args.hull:
+                region_info["hull_pixels"] = int(read.hull_area.sum(dtype=np.int64))
+            if with_routes:
+                region_info.update(labelled=len(read.route_table))
+                region_info.update({name + s: stats[name + s] for name in read.stages for s in ("_regions", "_pixels")})
+        return (rec.stage_ms(), int((read.counts > 0).sum()), int(read.counts.sum()), st, int(st.read_back.numel()), region_info,
+                planned["windows"], planned["ms"])
 
     for _ in range(args.warmup):
         one_page()
@@ -356,11 +255,10 @@ def main(argv=None):
         rec = _lib.stop_timing()
         smooth_split = {n: {"median": round(statistics.median(v[0] for v in rec[n]), 4), "min": round(min(v[0] for v in rec[n]), 4),
                             "max": round(max(v[0] for v in rec[n]), 4)} for n in split_names}
-    n_sel, n_text, keep, windows = runs[0][1], runs[0][2], runs[0][3], runs[0][6]
+    n_sel, n_text, state, windows = runs[0][1], runs[0][2], runs[0][3], runs[0][6]
     n_fill = n_sel if windows is None else len(windows[0])
-    if windows is not None:                                 # the same two slots of the timeline, other kernels
-        stages[stages.index("page_tiles_fill")], stages[stages.index("compose_page_u8")] = "page_windows_fill", "compose_page_windows_u8"
-    ms = {s: [r[0][i] for r in runs] for i, s in enumerate(stages)}
+    stages = [s for s in runs[0][0] if s not in ("joined", "planned")]      # those two marks close no stage
+    ms = {s: [r[0][s] for r in runs] for s in stages}
     med = {s: statistics.median(v) for s, v in ms.items()}
 
     # bytes each kernel has to move ("page pipeline")
@@ -404,7 +302,7 @@ def main(argv=None):
             vals.append((time.perf_counter() - t0) * 1e3)
         return {"median_ms": round(statistics.median(vals), 4), "min_ms": round(min(vals), 4), "max_ms": round(max(vals), 4)}
 
-    page_d, text, out, tiles, text_s = keep
+    page_d, text, text_s = state.page_d, state.text, state.text_s
     # (a) the parent's route for the mask stage: the page's logits to the host, threshold + 3 x 3 max-pool with nine torch.maximum
     stitched = torch.randn(1, 1, h, w, device=dev)
 
@@ -471,7 +369,7 @@ def main(argv=None):
     if args.hull:
         text1, _ = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)
         labels1, packed1 = RG._text_regions(text1, args.connectivity, args.min_area, args.max_regions, g)
-        table1 = RG.unpack_regions(packed1.cpu().numpy(), g.count, args.max_regions)[1]
+        table1 = RG.ReadBack(g.count, args.max_regions).unpack(packed1.cpu().numpy()).table
         try:
             from PIL import Image, ImageDraw
             from scipy.spatial import ConvexHull, QhullError
