@@ -13,6 +13,10 @@ into the mask on the device (the reference demo's ``cv2.convexHull`` step), so t
 ``--group G`` groups the regions that lie within G pixels of one another into blocks on the device first (a G of about the line spacing
 makes a speech bubble's lettering one block): ``--min-area``, ``--hull``, ``--flat`` and ``--pack`` then work per block and ``--boxes``
 outlines the blocks, the boxes a translation would be typeset into.
+``--seed P`` (a probability, ``--threshold`` <= P < 1) makes the cut a hysteresis threshold: ``--threshold`` may then be low enough to catch
+faint and small lettering, and a region (with ``--group``: a block) stays text only if the segmenter gave at least ``--min-seeds N`` (default
+1) of its pixels more than P; the others are dropped on the device before anything is inpainted.  ``examples/evaluate.py --task eraser``
+scores a P on raw / clean pairs.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 ``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
@@ -84,6 +88,9 @@ def main(argv=None):
     ap.add_argument("--tone-period", type=int, default=12, metavar="N", help="the longest period along each axis --tone looks for (2..16)")
     ap.add_argument("--group", type=int, default=None, metavar="G", help="group text regions within G pixels (1..64) into blocks: --min-area, --hull, "
                     "--flat and --pack then work per block, --boxes draws the block boxes")
+    ap.add_argument("--seed", type=float, default=None, metavar="P", help="keep a text region only if some pixel of it has a text probability above P "
+                    "(--threshold <= P < 1): a hysteresis threshold")
+    ap.add_argument("--min-seeds", type=int, default=1, metavar="N", help="the pixels above --seed a region needs to stay")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: fill the holes with T.HarmonicFill, without an inpainting net")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
     args = ap.parse_args(argv)
@@ -103,7 +110,7 @@ def main(argv=None):
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
                           seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group,
                           smooth=args.smooth, smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
-                          tone_period=args.tone_period)
+                          tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -136,6 +143,8 @@ def main(argv=None):
         st = eraser.last_stats
         print("%s: %d x %d, %d of %d tiles inpainted, text fraction %.4f" %
               (name, page.shape[0], page.shape[1], st["selected"], st["tiles"], float((mask > 0).mean())))
+        if args.seed is not None:
+            print("%s: %d text regions (%d pixels) without a pixel above %g dropped" % (name, st["seed_dropped"], st["seed_dropped_pixels"], args.seed))
         if args.pack:
             print("%s: %s, the grid would have sent %d tiles" % (name, "%d windows on the text regions" % st["windows"] if st["packed"]
                                                                   else "no fewer windows than tiles: the grid's tiles", st["grid_selected"]))

@@ -13,10 +13,13 @@ small result.  Needs an MI355X (the models have no CPU path).  Prints ONE JSON l
 Folders are what ``TextSegmentationData`` / ``ImageInpaintingData`` take.  For segmentation the line carries the sweep and
 ``suggested_eraser_threshold``: the probability with the best F1, to be passed as ``TextEraser(threshold=...)``.
 ``--task eraser`` pairs the files of the two folders by name (without the extension) and takes the eraser switches of
-``examples/erase_text.py`` (``--tile``, ``--min-area``, ``--hull``, ``--group``, ``--flat``, ``--smooth``, ``--tone``, ``--filler`` ...); the
+``examples/erase_text.py`` (``--tile``, ``--min-area``, ``--hull``, ``--group``, ``--seed``, ``--flat``, ``--smooth``, ``--tone``, ``--filler`` ...); the
 truth mask comes from each pair as the reference's ``Dataloader`` derives it (``--brightness-difference``, ``--truth-dilate``).  The line
 carries ``mask`` (precision / recall / F1 / IoU of the eraser's mask), ``fill`` and ``leftover`` (the error where the eraser painted and
 where it did not) and ``routes``: per route -- ``flat``, ``smooth``, ``tone``, ``net`` -- the regions it took and how well it repaired them.
+With ``--seed P`` (and ``--min-seeds N``) the same pairs are also run through the same eraser WITHOUT the seed, and the line gains
+``without_seed``: that run's ``mask``, so that the precision bought and the recall paid for a P stand side by side; ``seed_dropped`` /
+``seed_dropped_pixels`` are the regions the seed took out, over all pages.
 The eraser's line is strict JSON: a ratio over nothing (a route that took no region) is ``null``, the PSNR of an error of zero ``"inf"``.
 """
 import argparse
@@ -113,13 +116,31 @@ def eraser_main(args):
         if args.fill_checkpoint:
             fill.load_state_dict(torch.load(args.fill_checkpoint, map_location="cpu"))
         fill = fill.to(dev).eval()
-    eraser = T.TextEraser(seg.to(dev).eval(), fill, tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
-                          tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, seg_long_side=args.seg_long_side,
-                          hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth,
-                          smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
-                          tone_period=args.tone_period)
-    pairs = synthetic_pairs(args.synthetic, *args.synthetic_size) if args.synthetic else folder_pairs(args.raw_folder, args.clean_folder)
-    res = T.evaluate_eraser(eraser, pairs, T.EraserMetrics(args.brightness_difference, args.truth_dilate, ssim=args.ssim))
+    seg = seg.to(dev).eval()
+
+    class Counting(T.TextEraser):
+        """sums what the seed dropped over the pages"""
+        dropped = dropped_pixels = 0
+
+        def __call__(self, page):
+            out = super().__call__(page)
+            self.dropped += self.last_stats.get("seed_dropped", 0)
+            self.dropped_pixels += self.last_stats.get("seed_dropped_pixels", 0)
+            return out
+
+    def make(seed):
+        return Counting(seg, fill, tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
+                        tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, seg_long_side=args.seg_long_side,
+                        hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth,
+                        smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
+                        tone_period=args.tone_period, seed=seed, min_seeds=args.min_seeds)
+    make_pairs = lambda: synthetic_pairs(args.synthetic, *args.synthetic_size) if args.synthetic else folder_pairs(args.raw_folder, args.clean_folder)
+    eraser = make(args.seed)
+    res = T.evaluate_eraser(eraser, make_pairs(), T.EraserMetrics(args.brightness_difference, args.truth_dilate, ssim=args.ssim))
+    if args.seed is not None:
+        plain = T.evaluate_eraser(make(None), make_pairs(), T.EraserMetrics(args.brightness_difference, args.truth_dilate))
+        res.update(seed=args.seed, min_seeds=args.min_seeds, seed_dropped=eraser.dropped, seed_dropped_pixels=eraser.dropped_pixels,
+                   without_seed=plain["mask"])
     pages = [dict(sums=[int(v) for v in p["page"]], regions=len(p["rows"]), **({"ssim": p["ssim"]} if "ssim" in p else {})) for p in res.pop("pages")]
     line = {"task": "eraser", "seg_model": args.seg_model, "fill_model": "HarmonicFill" if args.filler == "harmonic" else args.fill_model,
             "pages": len(pages), **res, "per_page": pages}
@@ -161,6 +182,8 @@ def main(argv=None):
     ap.add_argument("--tone-ring", type=int, default=8, metavar="N")
     ap.add_argument("--tone-period", type=int, default=12, metavar="N")
     ap.add_argument("--group", type=int, default=None, metavar="G")
+    ap.add_argument("--seed", type=float, default=None, metavar="P", help="eraser: keep a text region only if some pixel of it has a probability above P")
+    ap.add_argument("--min-seeds", type=int, default=1, metavar="N")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"])
     ap.add_argument("--sweeps", type=int, default=8, metavar="N")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded synthetic images instead of a folder")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 17
+#define TSII_ABI_VERSION 18
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -956,6 +956,45 @@ int tsii_pair_text_mask(const uint8_t* raw, const uint8_t* clean, int h, int w, 
 size_t tsii_page_scores_ws_bytes(int h, int w, int max_rows);
 int tsii_page_scores(const uint8_t* out, const uint8_t* clean, const uint8_t* mask, const uint8_t* truth, const int* labels,
                      const int* table, int n_rows, int h, int w, int64_t* page, int64_t* rows, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- K19: seeded regions (csrc/seeds.hip) -- the second half of a hysteresis threshold: the plane was cut at a low probability and
+ * labelled; a region (or block) stays only if at least min_seeds of its pixels are also set in a second plane, cut at a high one.  Runs
+ * behind tsii_text_regions or tsii_text_blocks, in front of everything that works on their outputs.  All integer: the same inputs give
+ * the same bits on every run.
+ * Inputs as those calls leave them: text uint8 [h,w] (non-zero = text) and labels int32 [h,w], BOTH REWRITTEN IN PLACE; table int32
+ * [max_regions,6] = {label, area, y0, x0, y1, x1} ascending in label, REWRITTEN IN PLACE; n_regions int32 [2] = {found, kept} ON THE
+ * DEVICE (the call does not read it on the host).  seed: uint8 [h,w], read only, never the text plane; a pixel is a SEED where its byte is
+ * non-zero.  n = min(max(n_regions[1], 0), max_regions) table rows are in use.
+ *   s[r], r < n              = the number of pixels p with labels[p] == table[r][0] and seed[p] != 0.  A seed whose label is 0 or in no row
+ *                              counts nowhere.
+ *   row r is KEPT iff s[r] >= min_seeds; the others are DROPPED.  Kept regions beyond the table (kept > max_regions) have no row, are not
+ *   judged and stay, as they get no hull and no route.  With k = the number of kept rows:
+ *   labels[p], text[p]       = 0 for the pixels of dropped rows; every other byte of both planes is unchanged (text keeps its non-zero
+ *                              values, whatever they are).
+ *   table                    : the kept rows move to rows 0 .. k - 1 in their order.  The rows from n on are not touched.  Rows k .. n - 1
+ *                              keep what they held on entry (the rows that stood there) where the table held every region
+ *                              (n_regions[1] <= max_regions on entry).  Where it was cut, the count that is left may reach behind row
+ *                              k - 1, so these rows become EMPTY rows {INT_MAX, 0, 0, 0, 0, 0}: the label column still ascends, no pixel
+ *                              has that label, and every tsii_* call behind this one finds nothing for such a row (no hull, no ring,
+ *                              no route).  An empty row on entry is never judged and stays: a caller tells the rows of regions from the
+ *                              empty ones by count, min(n_regions[1] + dropped[0], max_regions) - dropped[0] summed over its calls.
+ *   members, NULL or int32 [max_regions] (the column of tsii_text_blocks): compacted with the table, the same rule; 0 in an empty row.
+ *   seeds, int32 [max_regions]: seeds[j] = s of the row that is now row j, j < k; the entries from k on are not touched.
+ *   n_regions[1]             = its value on entry - (n - k); n_regions[0] is unchanged.
+ *   dropped, int32 [2]       = {n - k, the summed area column of the dropped rows}.
+ *   core_count: NULL (tile and halo are ignored), or int32 [ty*tx] on the K8 tile geometry: cleared by the call, then the number of
+ *     pixels with text != 0 of the REDUCED plane in each tile core (integer atomics: independent of block order).
+ * A second call on the same buffers with the same seed plane drops nothing and changes nothing but dropped = {0, 0}.
+ * No allocation, no host synchronisation, everything on the caller's stream; no grid-wide barrier and no waiting on another block.
+ * ws: tsii_region_seeds_ws_bytes(h, w, max_regions) bytes (0: geometry refused), 4-byte aligned; it needs nothing cleared beforehand and
+ * holds nothing a later call depends on (three words per table row: the counts, the labels on entry and the verdicts).
+ * Refused (non-zero return, tsii_last_error, nothing written): min_seeds < 1; h or w < 1; h*w > 2^31 - 2; max_regions < 1; a NULL among
+ * text, labels, seed, table, n_regions, seeds, dropped, ws; seed == text; a bad tile geometry while core_count != NULL.
+ * The count read from n_regions is clamped to max_regions, a row found by the binary search over the label column lies below it and
+ * nothing is indexed by a label: a table that does not belong to the labels gives wrong numbers, never an access outside the buffers. */
+size_t tsii_region_seeds_ws_bytes(int h, int w, int max_regions);
+int tsii_region_seeds(uint8_t* text, int* labels, const uint8_t* seed, int h, int w, int* table, int* n_regions, int max_regions,
+                      int min_seeds, int tile, int halo, int* core_count, int* seeds, int* members, int* dropped, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -27,6 +27,10 @@ the pixel a whole number of periods away (``csrc/tone.hip``; "K17: tone regions"
 
 With ``group`` the regions are first grouped into blocks of lettering on the device (``csrc/blocks.hip``; "K15: text blocks"): the area
 filter, the hulls, the flat stage and ``pack`` then judge, fill, paint and place whole blocks instead of single glyphs.
+
+With ``seed`` the one cut at ``threshold`` becomes a hysteresis threshold: a region (with ``group``: a block) stays text only if the
+segmenter was sure, at the probability ``seed``, somewhere inside it (``csrc/seeds.hip``; "K19: seeded regions").  What is dropped leaves the
+plane, the labels and the table on the device, in front of the hulls, the routes and the page's one synchronisation.
 """
 from contextlib import contextmanager
 from dataclasses import dataclass
@@ -40,8 +44,8 @@ from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .masks import MaskParts
-from .regions import (ReadBack, _flat_regions, _region_hulls, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args,
-                      check_flat_args, check_region_args, check_smooth_args, check_tone_args)
+from .regions import (ReadBack, _flat_regions, _region_hulls, _region_seeds, _smooth_regions, _text_blocks, _text_regions, _tone_regions,
+                      check_block_args, check_flat_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
 
 
 class TileGrid(NamedTuple):
@@ -283,7 +287,7 @@ def _eval_mode(*nets):
 # mark before it: a stage's time on the stream is the time between those two.  Three marks close no stage: "start" (nothing is enqueued
 # yet), "joined" (the read-back tensor is formed; "counts_d2h" behind it is the copy alone) and "planned" (the host has selected the
 # tiles or planned the windows and uploaded their small index tensors).
-STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "hulls",
+STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "seeds", "hulls",
                "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler",
                "compose_page_u8", "compose_page_windows_u8", "download")
 
@@ -295,7 +299,7 @@ class PageState:
     working resolution); ``src``: the page the filler and compose see (``page_d``, or what the flat, smooth and tone stages painted);
     ``both``: clean and mask in one buffer (one download), ``mask_u8`` its mask part; ``compose_mask``: the plane compose writes its
     mask to (``mask_u8``, or scratch where a stage wrote the page's mask already); ``read_back``: the one tensor the synchronisation
-    copies."""
+    copies; ``logits``: the segmenter's, kept for the seeds stage only (None without ``seed``)."""
     g: TileGrid
     gs: TileGrid
     page_d: torch.Tensor
@@ -306,6 +310,7 @@ class PageState:
     mask_u8: torch.Tensor
     compose_mask: torch.Tensor
     read_back: torch.Tensor
+    logits: torch.Tensor = None
 
 
 class TextEraser:
@@ -387,6 +392,17 @@ class TextEraser:
     of the page); ``last_stats`` gains ``blocks``.  Behind ``hull`` the flat stage labels the filled plane as before, ungrouped: hulls
     are solid.  Still one synchronisation.  ``None`` (the default): none of this runs.
 
+    ``seed=P`` (a probability, ``threshold <= P < 1``; turns the regions path on as well): a hysteresis threshold.  ``threshold`` cuts low,
+    so that faint and small lettering is caught; a region -- with ``group`` a block -- then stays only if at least ``min_seeds`` of its
+    pixels have ``sigmoid(logit) > P`` (the seed plane: not dilated; with ``seg_long_side`` brought onto the page like the text plane, of
+    which it is a subset).  The regions that do not are dropped on the device right behind ``min_area`` and the blocks, in front of
+    everything else: they are not in the returned mask, select no tile, get no hull and no route, and ``pack`` plans no window on them.
+    With ``group`` a faint mark beside a confident glyph stays, as a member of the glyph's block.  Kept regions beyond ``max_regions``
+    are not judged and stay.  ``last_regions`` gains ``seeds`` (numpy int32, the seed pixels of each table row; ``table``, ``kept`` and
+    ``members`` are those of the regions that stayed), ``last_stats`` gains ``seed_dropped`` and ``seed_dropped_pixels``.  Choose ``P`` with
+    ``evaluate_eraser`` on raw / clean pairs: the mask's precision and recall with and without it.  Still one synchronisation.  ``None``
+    (the default): none of this runs.
+
     The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
     the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
     ``clean`` equals the page wherever ``mask`` is 0.
@@ -395,7 +411,7 @@ class TextEraser:
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
                  max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
-                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12):
+                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -424,7 +440,13 @@ class TextEraser:
             check_tone_args(0 if tone is None else tone, tone_ring, tone_period)
         self.tone, self.tone_ring, self.tone_period = None if tone is None else int(tone), int(tone_ring), int(tone_period)
         self.routes = self.flat is not None or self.smooth is not None or self.tone is not None
-        self.regions = bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
+        if seed is not None and not float(threshold) <= float(seed) < 1.0:
+            raise ValueError(f"seed {seed} must be a probability in [threshold, 1) = [{threshold}, 1)")
+        check_seed_args(min_seeds)
+        self.seed, self.min_seeds = None if seed is None else float(seed), int(min_seeds)
+        self.seed_logit = None if seed is None else logit_of(seed)
+        self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
+                        or self.seed is not None)
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -472,7 +494,7 @@ class TextEraser:
     def _layout(self, g):
         """the page's read-back tensor: what rides where in it"""
         return ReadBack(g.count, self.max_regions, self.hull, self.group is not None, self.flat is not None, self.smooth is not None,
-                        self.tone is not None, regions=self.regions)
+                        self.tone is not None, regions=self.regions, seeds=self.seed is not None)
 
     def _route(self, name, src, text, g, labels, own, mask_u8):
         """the flat, smooth or tone stage: fill the regions it takes and take them out of the text plane in place -> the filled page (a new
@@ -537,25 +559,32 @@ class TextEraser:
         off = (h * w * 3 + 15) // 16 * 16               # clean + mask in one buffer (one download); the kernels want both 4-byte aligned
         both = torch.empty((off + h * w,), dtype=torch.uint8, device=self.device)
         mask_u8 = both[off:].view(h, w)
-        st = PageState(g, gs, page_d, text, text_s, page_d, both, mask_u8, mask_u8, counts)
+        st = PageState(g, gs, page_d, text, text_s, page_d, both, mask_u8, mask_u8, counts, logits if self.seed is not None else None)
         if self.regions:
             self._enqueue_regions(st)
         self._mark("joined")
         return st
 
     def _enqueue_regions(self, st):
-        """the regions path of phase 1, in place on ``st.text``: labelling, blocks, hulls and the flat, smooth and tone stages"""
+        """the regions path of phase 1, in place on ``st.text``: labelling, blocks, seeds, hulls and the flat, smooth and tone stages"""
         g, text, lay = st.g, st.text, self._layout(st.g)
         second = whole = None
         if self.group is None:
-            self.last_labels, first = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=lay.tail)
+            self.last_labels, first = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=lay.tail + lay.extra)
+            if lay.seeded:                              # the seeds' room rides behind the first tensor
+                whole, first = first, first[lay.first]
             self._mark("regions")
         else:                                           # every region is labelled and no table is made: the blocks stage filters
             labels, every = _text_regions(text, self.connectivity, 0, 0, g)
             self._mark("regions")
             self.last_labels, first, whole = _text_blocks(text, labels, every[lay.n_regions], self.group, self.min_area, self.max_regions, g,
-                                                          tail=lay.tail)
+                                                          tail=lay.tail, extra=lay.extra)
             self._mark("blocks")
+        if lay.seeded:
+            members, room = lay.seed_room(whole)
+            _region_seeds(text, self.last_labels, self._seed_plane(st), first, room, self.max_regions, self.min_seeds, members, g)
+            st.logits = None
+            self._mark("seeds")
         if self.hull:
             _region_hulls(text, self.last_labels, first, self.max_regions, g)
             self._mark("hulls")
@@ -571,13 +600,20 @@ class TextEraser:
             st.compose_mask = torch.empty_like(st.mask_u8)      # the first stage wrote the page's mask; compose's, of the reduced plane, is scratch
         st.read_back = lay.join(first, second, whole)
 
+    def _seed_plane(self, st):
+        """the seed plane on the page's grid: ``logit > logit_of(seed)``, not dilated, through the kernels that made the text plane"""
+        seed, _ = _tiles_text_mask(st.logits, st.gs, self.seed_logit, 1)
+        if st.gs is not st.g:
+            seed, _ = _text_plane_up(seed, st.g)
+        return seed
+
     def _read_back(self, st):
         """phase 2: the one synchronisation before the download -> ``regions.PageRead``"""
         host = st.read_back.cpu().numpy()
         self._mark("counts_d2h")
         read = self._layout(st.g).unpack(host)
         if self.regions:
-            named = ("table", "found", "kept", "truncated", "members", "components", "hull_area")
+            named = ("table", "found", "kept", "truncated", "members", "components", "hull_area", "seeds")
             self.last_regions = {k: getattr(read, k) for k in named if getattr(read, k) is not None}
             self.last_regions.update(read.stages)
         return read
@@ -618,6 +654,8 @@ class TextEraser:
         if self.group is not None:
             self.last_stats.update(blocks=read.kept)
         self.last_stats.update(route_stats)
+        if self.seed is not None:
+            self.last_stats.update(seed_dropped=read.seed_dropped, seed_dropped_pixels=read.seed_dropped_pixels)
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)

@@ -25,6 +25,10 @@ whose ring repeats under one integer shift is filled by copying the pixel a whol
 (Chebyshev distance) of some pixel of the other, and so on through their neighbours (``tsii_text_blocks``, ``csrc/blocks.hip``; "K15:
 text blocks").  The block labels and the block table have the form of the regions' own, so the hulls, the flat stage and the window
 planner work per block behind it.
+
+``seeded_regions`` is a hysteresis threshold: the plane was cut at a low probability; a region (with ``gap``: a block) stays only where at
+least ``min_seeds`` of its pixels are set in a second plane, cut at a high one (``tsii_region_seeds``, ``csrc/seeds.hip``; "K19: seeded
+regions").  The dropped regions leave the plane, the labels and the table on the device, before the read-back.
 """
 from typing import NamedTuple
 
@@ -112,6 +116,23 @@ class TextBlocks(NamedTuple):
     components: int
 
 
+class SeededRegions(NamedTuple):
+    """``mask``: uint8 ``[H, W]`` of 0 / 255, the text of the regions that hold a seed.  ``labels`` / ``table`` / ``found`` / ``truncated``: as
+    in ``TextRegions`` (with ``gap``: ``TextBlocks``), of those regions only; ``kept``: the regions left after both filters.  ``seeds``: numpy
+    int32 ``[n]``, the seed pixels of each table row.  ``dropped`` / ``dropped_pixels``: the regions that held fewer than ``min_seeds`` seeds
+    and their summed area.  ``members``: numpy int32 ``[n]`` with ``gap``, else None."""
+    mask: object
+    labels: object
+    table: np.ndarray
+    seeds: np.ndarray
+    found: int
+    kept: int
+    dropped: int
+    dropped_pixels: int
+    truncated: bool
+    members: np.ndarray = None
+
+
 def _check_int_range(name, value, lo, hi):
     if isinstance(value, bool) or int(value) != value or not lo <= value <= hi:
         raise ValueError(f"{name} {value} must be an integer {lo}..{hi}")
@@ -128,6 +149,10 @@ def check_region_args(connectivity, min_area, max_regions):
         raise ValueError(f"min_area {min_area} must be an integer >= 0")
     if int(max_regions) != max_regions or max_regions < 1:
         raise ValueError(f"max_regions {max_regions} must be an integer >= 1")
+
+
+def check_seed_args(min_seeds):
+    _check_int_range("min_seeds", min_seeds, 1, 2 ** 31 - 1)
 
 
 def check_flat_args(tol, ring):
@@ -177,7 +202,9 @@ class PageRead(NamedTuple):
     left).  ``table`` / ``found`` / ``kept`` / ``truncated``: the first labelling's (with ``group``: the blocks').  ``hull_area``,
     ``members`` / ``components``: with ``hull`` / ``group``, else None.  ``route_table`` (the components the flat, smooth and tone stages
     worked on), ``stages`` and ``gone`` as ``unpack_routes`` gives them: None, {} and None without such a stage.  ``plan_table`` /
-    ``plan_truncated``: the regions that still hold text, for ``plan_fill_windows``.  Without the regions path all but ``counts`` is None."""
+    ``plan_truncated``: the regions that still hold text, for ``plan_fill_windows``.  ``seeds`` (the seed pixels of each table row),
+    ``seed_dropped`` / ``seed_dropped_pixels`` (the rows ``tsii_region_seeds`` took out, their summed area): with ``seeds``, else None.
+    Without the regions path all but ``counts`` is None."""
     counts: np.ndarray
     table: np.ndarray = None
     found: int = None
@@ -191,6 +218,9 @@ class PageRead(NamedTuple):
     gone: np.ndarray = None
     plan_table: np.ndarray = None
     plan_truncated: bool = None
+    seeds: np.ndarray = None
+    seed_dropped: int = None
+    seed_dropped_pixels: int = None
 
 
 class ReadBack:
@@ -199,9 +229,11 @@ class ReadBack:
     blocks' with ``group`` -- whose ``tail`` words are the hull areas with ``hull``, else the route rows (``RouteLayout``).  ``second`` is
     there with ``hull`` and a route stage: the tensor of the labelling of the filled plane, in ``RouteLayout``'s form (``second_tail``
     words behind its table).  The last part is there with ``group``.  ``routes`` is the ``RouteLayout`` of the tensor the route stages
-    work on, the second where there is one, else the first.  Without ``regions`` the tensor is the ``nt`` core counts alone."""
+    work on, the second where there is one, else the first.  Without ``regions`` the tensor is the ``nt`` core counts alone.  With ``seeds``
+    its LAST ``extra`` words are ``[seeds (max_regions) | dropped, dropped pixels]`` of ``tsii_region_seeds``: room the first labelling's
+    tensor -- with ``group`` the blocks' ``whole`` -- is allocated with (``seed_room``), so that nothing in front of it moves."""
 
-    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True):
+    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True, seeds=False):
         n = int(max_regions)
         self.routes = RouteLayout(nt, n, flat, smooth, tone)
         self.regions, self.hull, self.group = bool(regions), bool(hull), bool(group)
@@ -213,10 +245,22 @@ class ReadBack:
         self.own = slice(self.first.stop, self.first.stop + self.routes.words) if two else self.first
         self.members = slice(self.own.stop, self.own.stop + n)
         self.words = self.members.stop + 1 if self.group else self.own.stop if self.regions else int(nt)
+        self.seeded = bool(seeds) and self.regions
+        self.extra = n + 2 if self.seeded else 0
+        self.seed_words, self.seed_dropped = slice(self.words, self.words + n), slice(self.words + n, self.words + self.extra)
+        self.words += self.extra
+
+    def seed_room(self, whole):
+        """(members, room) on the device for ``_region_seeds``: ``whole`` is the first labelling's tensor as allocated, ``[first | members,
+        components (with group) | seeds, dropped]``; ``members`` is None without ``group``"""
+        n = self.routes.max_regions
+        assert self.seeded and whole.numel() == self.first.stop + (n + 1 if self.group else 0) + self.extra
+        return (whole[self.first.stop:self.first.stop + n] if self.group else None), whole[whole.numel() - self.extra:]
 
     def join(self, first, second=None, whole=None):
         """the tensor to copy, from what the stages left on the device: ``first``, ``second`` (None where the route stages worked on
-        ``first``) and, with ``group``, ``whole``: ``_text_blocks``' tensor, whose front ``first`` is.  Copies only where a tensor has to
+        ``first``) and, with ``group`` or ``seeds``, ``whole``: the tensor as allocated (``_text_blocks``', or ``_text_regions``' with the
+        seeds' room behind it), whose front ``first`` is.  Copies only where a tensor has to
         ride between ``first`` and the members."""
         if second is None:
             return first if whole is None else whole
@@ -226,7 +270,9 @@ class ReadBack:
         """the host copy of the joined tensor -> ``PageRead``; ``host`` is not written, the tables and columns are copies"""
         if not self.regions:
             return PageRead(host, stages={})
-        counts, table, found, kept, truncated = unpack_regions(host[self.first], self.routes.nt, self.routes.max_regions)
+        # with seeds: where the table was cut on entry, the count that is left reaches into empty rows (include/tsii_hip.h, K19)
+        dropped = int(host[self.seed_dropped][0]) if self.seeded else 0
+        counts, table, found, kept, truncated = unpack_regions(host[self.first], self.routes.nt, self.routes.max_regions, dropped)
         n = len(table)
         read = PageRead(counts, table, found, kept, truncated, stages={}, plan_table=table, plan_truncated=truncated)
         if self.hull:
@@ -234,8 +280,11 @@ class ReadBack:
         if self.group:
             read = read._replace(members=host[self.members][:n].copy(), components=int(host[self.members.stop]))
         if self.routes.stages:                          # behind the hulls: the filled plane's own components; all that follows works on them
-            counts, rtable, rtruncated, stages, gone = unpack_routes(host[self.own], self.routes)
+            counts, rtable, rtruncated, stages, gone = unpack_routes(host[self.own], self.routes, 0 if self.own != self.first else dropped)
             read = read._replace(counts=counts, route_table=rtable, stages=stages, gone=gone, plan_table=rtable[~gone], plan_truncated=rtruncated)
+        if self.seeded:
+            read = read._replace(seeds=host[self.seed_words][:n].copy(), seed_dropped=dropped,
+                                 seed_dropped_pixels=int(host[self.seed_dropped][1]))
         return read
 
 
@@ -259,12 +308,12 @@ def _text_regions(text, connectivity, min_area, max_regions, grid=None, tail=0):
     return labels, packed
 
 
-def _text_blocks(text, labels, counts, gap, min_area, max_regions, grid=None, tail=0):
+def _text_blocks(text, labels, counts, gap, min_area, max_regions, grid=None, tail=0, extra=0):
     """``tsii_text_blocks`` in place on the device plane ``text``, behind the ``_text_regions`` call (``min_area=0``, same ``grid``) that
     left ``labels`` and the device pair ``counts`` = its {found, kept} -> (block_labels, packed, whole).  ``packed`` has the layout
     ``_text_regions`` gives its own, ``[core counts | found, kept | table rows | tail words]``, of the BLOCKS: ``_region_hulls``
     and ``unpack_regions`` take it as it is, the flat, smooth and tone stages its slices (``RouteLayout``).  It is the front of ``whole``, the ONE tensor a caller reads back:
-    ``[packed | members (max_regions) | the components found]``."""
+    ``[packed | members (max_regions) | the components found | extra words]`` (``extra``: room for ``_region_seeds``)."""
     h, w = int(text.shape[0]), int(text.shape[1])
     n = int(max_regions)
     assert text.dtype == torch.uint8 and text.is_contiguous() and labels.shape == text.shape and labels.dtype == torch.int32
@@ -274,8 +323,8 @@ def _text_blocks(text, labels, counts, gap, min_area, max_regions, grid=None, ta
     nt = 0 if grid is None else grid.count
     front = nt + 2 + 6 * n + int(tail)
     block_labels = torch.empty((h, w), dtype=torch.int32, device=text.device)
-    whole = torch.zeros((front + n + 1,), dtype=torch.int32, device=text.device)
-    whole[front + n:].copy_(counts[:1])
+    whole = torch.zeros((front + n + 1 + int(extra),), dtype=torch.int32, device=text.device)
+    whole[front + n:front + n + 1].copy_(counts[:1])
     ws = ops._ws(nbytes, text)
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
     call("tsii_text_blocks", ptr(text), ptr(labels), h, w, int(gap), int(min_area), n, tile, halo, ptr(whole[:nt]) if nt else None,
@@ -298,6 +347,27 @@ def _region_hulls(text, labels, packed, max_regions, grid=None):
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
     call("tsii_region_hulls", ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, tile, halo,
          ptr(packed[:nt]) if nt else None, ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+
+
+def _region_seeds(text, labels, seed, packed, room, max_regions, min_seeds, members=None, grid=None):
+    """``tsii_region_seeds`` in place on the device planes ``text`` and ``labels``, right behind ``_text_regions`` or ``_text_blocks`` (same
+    ``grid``): ``packed`` is that call's tensor, ``[core counts | found, kept | table | ...]``, whose table is compacted, whose kept count
+    is lowered and whose core counts are rewritten for the reduced plane; ``members`` the blocks' column, compacted with the table;
+    ``room``: ``max_regions + 2`` device words, ``[seeds | dropped, dropped pixels]``.  ``seed``: the uint8 seed plane, read only."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    nt = 0 if grid is None else grid.count
+    n = int(max_regions)
+    assert seed.shape == text.shape and all(t.dtype == torch.uint8 and t.is_contiguous() and t.device == text.device for t in (text, seed))
+    assert labels.shape == text.shape and labels.dtype == torch.int32 and labels.is_contiguous()
+    assert packed.numel() >= nt + 2 + 6 * n and room.numel() == n + 2 and all(t.dtype == torch.int32 and t.device == text.device for t in (packed, room))
+    assert members is None or (members.numel() == n and members.dtype == torch.int32 and members.is_contiguous())
+    nbytes = int(_lib.lib().tsii_region_seeds_ws_bytes(h, w, n))
+    if nbytes == 0:
+        raise ValueError(f"text plane of {h} x {w} pixels, {n} regions: out of range")
+    ws = ops._ws(nbytes, text)
+    tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
+    call("tsii_region_seeds", ptr(text), ptr(labels), ptr(seed), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, int(min_seeds), tile, halo,
+         ptr(packed[:nt]) if nt else None, ptr(room[:n]), ptr(members), ptr(room[n:]), ptr(ws), _lib.stream())
 
 
 def _flat_regions(page, text, labels, table, n_regions, rows, max_regions, ring, tol, painted, mask=None, grid=None, core_count=None):
@@ -383,12 +453,12 @@ def unpack_flat(rows_h, n):
     return rows[:, 0] != 0, rows[:, 1:4].astype(np.uint8), rows[:, 4].copy()
 
 
-def unpack_routes(own_h, layout):
-    """host copy of the stages' tensor -> (core counts, table, truncated, stages, gone).  ``stages``: per enabled stage the dict
+def unpack_routes(own_h, layout, dropped=0):
+    """host copy of the stages' tensor -> (core counts, table, truncated, stages, gone); ``dropped``: as for ``unpack_regions``.  ``stages``: per enabled stage the dict
     ``TextEraser.last_regions`` carries under its name (``table`` and the stage's columns: ``is_flat`` / ``colour`` / ``ring_pixels``, ...);
     ``gone``: bool per table row, some stage took the region out of the plane (it has no text left: its rows of the later stages are
     empty)."""
-    counts_h, table, _, _, truncated = unpack_regions(own_h, layout.nt, layout.max_regions)
+    counts_h, table, _, _, truncated = unpack_regions(own_h, layout.nt, layout.max_regions, dropped)
     columns = {"flat": (unpack_flat, ("is_flat", "colour", "ring_pixels")),
                "smooth": (unpack_smooth, ("is_smooth", "step", "ring_pixels")),
                "tone": (unpack_tone, ("is_tone", "shift", "err", "step", "ring_pixels"))}
@@ -400,10 +470,11 @@ def unpack_routes(own_h, layout):
     return counts_h, table, truncated, stages, gone
 
 
-def unpack_regions(packed_h, nt, max_regions):
-    """host copy of ``packed`` -> (core counts, table, found, kept, truncated)"""
+def unpack_regions(packed_h, nt, max_regions, dropped=0):
+    """host copy of ``packed`` -> (core counts, table, found, kept, truncated).  ``dropped``: the rows ``tsii_region_seeds`` took out of the
+    table behind the labelling: the table had ``min(kept + dropped, max_regions)`` rows then, and was cut if that is ``max_regions``."""
     found, kept = int(packed_h[nt]), int(packed_h[nt + 1])
-    n = min(kept, int(max_regions))
+    n = min(kept + int(dropped), int(max_regions)) - int(dropped)
     table = packed_h[nt + 2:nt + 2 + 6 * n].reshape(n, 6).copy()
     return packed_h[:nt], table, found, kept, kept > n
 
@@ -533,6 +604,36 @@ def text_blocks(mask_u8, gap, connectivity=8, min_area=0, max_regions=4096, devi
     block_labels, _, whole = _text_blocks(plane, labels, counts, gap, min_area, max_regions)
     r = ReadBack(0, max_regions, group=True).unpack(whole.cpu().numpy())
     return TextBlocks(_like(plane * 255, mask_u8), _like(block_labels, mask_u8), r.table, r.members, r.found, r.kept, r.components)
+
+
+def seeded_regions(mask_u8, seed_u8, min_seeds=1, connectivity=8, min_area=0, gap=None, max_regions=4096, device=None) -> SeededRegions:
+    """Hysteresis threshold on regions.  ``mask_u8``: ``[H, W]`` uint8, the plane cut at the LOW threshold; ``seed_u8``: the same shape, the
+    plane cut at the HIGH one; numpy or torch, host or device, non-zero = set, neither is modified.  The connected regions of the mask
+    (``connectivity`` 4 or 8) below ``min_area`` pixels are dropped first, as in ``text_regions``; a kept region then stays only if at least
+    ``min_seeds`` of its pixels are seeds.  With ``min_seeds=1`` the mask that comes back is the classic hysteresis threshold: the
+    components of the low plane that contain a high pixel.  With ``gap`` (1..64) the regions are grouped into blocks first, as in
+    ``text_blocks``, and whole blocks are judged: a faint mark stays beside a confident glyph.  Kept regions beyond ``max_regions`` are not
+    judged and stay.  ``mask`` and ``labels`` come back the same kind and on the same device as ``mask_u8``; one synchronisation (the
+    read-back of the counts, the table and the seeds).  Host planes are computed on ``device`` (default ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_seed_args(min_seeds)
+    if gap is not None:
+        check_block_args(gap)
+    plane = _plane_on_device(mask_u8, device)
+    if tuple(seed_u8.shape) != tuple(plane.shape):
+        raise ValueError(f"seed plane {tuple(seed_u8.shape)} for a mask of {tuple(plane.shape)}")
+    seed = _plane_on_device(seed_u8, plane.device)
+    rb = ReadBack(0, max_regions, group=gap is not None, seeds=True)
+    if gap is None:
+        labels, whole = _text_regions(plane, connectivity, min_area, max_regions, tail=rb.extra)
+    else:
+        every, counts = _text_regions(plane, connectivity, 0, 0)
+        labels, _, whole = _text_blocks(plane, every, counts, gap, min_area, max_regions, extra=rb.extra)
+    members, room = rb.seed_room(whole)
+    _region_seeds(plane, labels, seed, whole[rb.first], room, max_regions, min_seeds, members)
+    r = rb.unpack(whole.cpu().numpy())
+    return SeededRegions(_like(plane * 255, mask_u8), _like(labels, mask_u8), r.table, r.seeds, r.found, r.kept, r.seed_dropped,
+                         r.seed_dropped_pixels, r.truncated, r.members)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

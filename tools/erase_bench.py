@@ -53,6 +53,11 @@ own pair of events and reports the tone regions.  Compare with a run on the same
 ``--group G`` (turns the regions stage on) adds the ``blocks`` stage (tsii_text_blocks, right behind the regions stage, which then labels
 every region and leaves the filter to the blocks): its own pair of events.  ``regions`` then counts blocks in ``found`` / ``kept`` and
 reports ``components`` and ``largest_block`` (members).  Compare with the same line without ``--group`` in the same session.
+
+``--seed P`` (turns the regions stage on) adds the ``seeds`` stage (the seed plane by tsii_tiles_text_mask at dilate 1 -- and tsii_text_plane_up
+with ``--seg-long-side`` -- then tsii_region_seeds, behind the regions / blocks stages) with its own pair of events; ``regions`` then reports
+``seed_dropped`` / ``seed_dropped_pixels``.  ``--faint SHARE`` gives that share of the blobs a logit of 1 (a probability of 0.73) instead of
+4, so that a ``P`` between the two has something to drop.  Compare with the same line without ``--seed`` in the same session.
 """
 import argparse
 import json
@@ -69,15 +74,17 @@ import torch  # noqa: E402
 import torch.nn.functional as F  # noqa: E402
 
 
-def blob_field(h, w, fraction, seed, rects=None):
-    """logits [h, w] of a page whose text is rectangular blobs covering about ``fraction`` of it (``rects``: a list that gets the blobs)"""
+def blob_field(h, w, fraction, seed, rects=None, faint=0.0):
+    """logits [h, w] of a page whose text is rectangular blobs covering about ``fraction`` of it (``rects``: a list that gets the blobs);
+    ``faint``: this share of the blobs, evenly among them, has a logit of 1 instead of 4"""
     rng = np.random.default_rng(seed)
     page = np.full((h, w), -4.0, np.float32)
-    target, covered = fraction * h * w, 0
+    target, covered, k = fraction * h * w, 0, 0
     while covered < target:
         bh, bw = int(rng.integers(30, 120)), int(rng.integers(60, 300))
         y, x = int(rng.integers(0, max(1, h - bh))), int(rng.integers(0, max(1, w - bw)))
-        page[y:y + bh, x:x + bw] = 4.0
+        page[y:y + bh, x:x + bw] = 1.0 if (k % 10) < round(10 * faint) else 4.0
+        k += 1
         covered += bh * bw
         if rects is not None:
             rects.append((y, x, bh, bw))
@@ -148,6 +155,9 @@ def main(argv=None):
     ap.add_argument("--tone-ring", type=int, default=8)
     ap.add_argument("--tone-period", type=int, default=12)
     ap.add_argument("--group", type=int, default=None, metavar="G", help="time the blocks stage (tsii_text_blocks): regions within G pixels form a block")
+    ap.add_argument("--seed", type=float, default=None, metavar="P", help="time the seeds stage (tsii_region_seeds): regions without a pixel above P are dropped")
+    ap.add_argument("--min-seeds", type=int, default=1)
+    ap.add_argument("--faint", type=float, default=0.0, metavar="SHARE", help="this share of the blobs has a logit of 1 instead of 4")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
     args = ap.parse_args(argv)
@@ -168,7 +178,7 @@ def main(argv=None):
         gs = P.tile_grid(hs, ws, args.tile, args.halo)
     with_seg = gs is not g
     rects = []
-    field = blob_field(h, w, 0.0 if args.all_text else args.text_fraction, 1, rects)
+    field = blob_field(h, w, 0.0 if args.all_text else args.text_fraction, 1, rects, args.faint)
     if args.bubbles is not None:
         page = bubble_page(h, w, rects, args.bubbles, 2)
     if args.ramps is not None:
@@ -185,14 +195,15 @@ def main(argv=None):
     with_smooth = args.smooth is not None
     with_tone = args.tone is not None
     with_routes = with_flat or with_smooth or with_tone
-    with_regions = args.min_area > 0 or args.hull or args.pack or with_blocks or with_routes
+    with_seeds = args.seed is not None
+    with_regions = args.min_area > 0 or args.hull or args.pack or with_blocks or with_routes or with_seeds
 
     def make(select):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
                           flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth, tone=args.tone,
-                          tone_ring=args.tone_ring, tone_period=args.tone_period)
+                          tone_ring=args.tone_ring, tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -235,6 +246,8 @@ def main(argv=None):
             region_info = {"found": read.found, "kept": read.kept, "truncated": read.truncated}
             if with_blocks:
                 region_info.update(components=read.components, largest_block=int(read.members.max()) if len(read.members) else 0)
+            if with_seeds:
+                region_info.update(seed_dropped=read.seed_dropped, seed_dropped_pixels=read.seed_dropped_pixels)
             if args.hull:
                 region_info["hull_pixels"] = int(read.hull_area.sum(dtype=np.int64))
             if with_routes:
@@ -277,6 +290,8 @@ def main(argv=None):
         bytes_["regions"] = 18 * npx        # local 1 + 4, measure 4, filter 4 + 4 + 1 ("text regions"); seams and statistics on top
     if with_blocks:                         # DESIGN.md, "text blocks": pack 4, dilate 1, the labelling of the dilated plane 18, min 4 (+ runs),
         bytes_["blocks"] = 48 * npx         # name 4 + 4 + 4, measure 4, filter 4 + 4 + 1
+    if with_seeds:                          # DESIGN.md, "seeded regions": the seed plane 4 + 1 (and its way up), count 1 (+ 4 on the seeds),
+        bytes_["seeds"] = 15 * npx + (nsp + npx if with_seg else 0)     # filter 4 + 1 (+ stores where a region goes)
     if args.hull:
         bytes_["hulls"] = 5 * npx + n_text  # extents 4 (labels), finish 1, the fill's stores at most once per final text pixel ("region hulls")
     if with_flat:                           # DESIGN.md, "flat regions": ring 1 (text) + apron, apply 3 + 1 in, 3 + 1 + 1 out, labels on the text
@@ -406,6 +421,7 @@ def main(argv=None):
         "d2h_before_download": {"stages": [s_ for s_ in stages if s_.endswith("_d2h")], "int32_words": runs[0][4]},
         "regions": runs[0][5], "host_route": host_route, "hull": args.hull, "host_route_hulls": host_route_hulls,
         "bubbles": args.bubbles, "flat": args.flat, "flat_ring": args.flat_ring if with_flat else None, "group": args.group,
+        "seed": args.seed, "min_seeds": args.min_seeds if with_seeds else None, "faint": args.faint,
         "ramps": args.ramps, "smooth": args.smooth, "smooth_split_ms": smooth_split,
         "tones": args.tones, "tone": args.tone, "tone_ring": args.tone_ring if with_tone else None,
         "tone_period": args.tone_period if with_tone else None,
