@@ -32,6 +32,10 @@ by copying the pixel a whole number of periods away, behind ``--smooth``.  The p
 ``--filler harmonic`` needs no inpainting checkpoint: the holes take the smooth continuation of their surroundings (``T.HarmonicFill``,
 ``--sweeps N`` Jacobi sweeps per level, default 8), the right fill for text on a gradient, a soft shadow or a sky; no inpainting net is
 built or loaded.
+``--blend`` takes what the inpainting net paints into the page in the gradient domain (seamless, Poisson composition): the net's own error at
+the pixels around every hole, continued harmonically into the hole (``--blend-sweeps N`` Jacobi sweeps per level, default 8) and added
+there, so that a patch whose content is right and whose level is a shade off no longer stands out.  Per tile, on the device, between the
+net and the page; ``examples/evaluate.py --task eraser --blend`` says on raw / clean pairs whether it helps a checkpoint.
 """
 import argparse
 import os
@@ -93,6 +97,8 @@ def main(argv=None):
     ap.add_argument("--min-seeds", type=int, default=1, metavar="N", help="the pixels above --seed a region needs to stay")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: fill the holes with T.HarmonicFill, without an inpainting net")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
+    ap.add_argument("--blend", action="store_true", help="seamless composition: correct the level of what the filler paints from its error around the holes")
+    ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --blend (0..16)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
@@ -110,7 +116,7 @@ def main(argv=None):
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
                           seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group,
                           smooth=args.smooth, smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
-                          tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds)
+                          tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend, blend_sweeps=args.blend_sweeps)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -154,6 +160,8 @@ def main(argv=None):
             print("%s: %d smooth text regions (%d pixels) filled harmonically without the inpainting net" % (name, st["smooth_regions"], st["smooth_pixels"]))
         if args.tone is not None:
             print("%s: %d tone text regions (%d pixels) filled from one period away without the inpainting net" % (name, st["tone_regions"], st["tone_pixels"]))
+        if args.blend:
+            print("%s: %d tiles or windows blended into the page" % (name, st["blended"]))
         if "seg_size" in st:
             print("%s: segmented at %d x %d (%d tiles)" % ((name,) + tuple(st["seg_size"]) + (st["seg_tiles"],)))
     print("Runtime :{:.3f} s -> {}".format(time.time() - t0, out_folder))

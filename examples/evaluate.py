@@ -20,6 +20,9 @@ where it did not) and ``routes``: per route -- ``flat``, ``smooth``, ``tone``, `
 With ``--seed P`` (and ``--min-seeds N``) the same pairs are also run through the same eraser WITHOUT the seed, and the line gains
 ``without_seed``: that run's ``mask``, so that the precision bought and the recall paid for a P stand side by side; ``seed_dropped`` /
 ``seed_dropped_pixels`` are the regions the seed took out, over all pages.
+With ``--blend`` (and ``--blend-sweeps N``) the filler's output is taken into the page in the gradient domain, the same pairs are also run
+through the same eraser WITHOUT the blend, and the line gains ``without_blend``: that run's ``fill`` and ``routes``, so that what the blend
+does to the painted pixels stands side by side; ``fill`` and ``routes["net"]`` are the rows to read.
 The eraser's line is strict JSON: a ratio over nothing (a route that took no region) is ``null``, the PSNR of an error of zero ``"inf"``.
 """
 import argparse
@@ -128,12 +131,12 @@ def eraser_main(args):
             self.dropped_pixels += self.last_stats.get("seed_dropped_pixels", 0)
             return out
 
-    def make(seed):
+    def make(seed, blend=args.blend):
         return Counting(seg, fill, tile=args.tile, halo=args.halo, dilate=args.dilate, threshold=args.threshold,
                         tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, seg_long_side=args.seg_long_side,
                         hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth,
                         smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
-                        tone_period=args.tone_period, seed=seed, min_seeds=args.min_seeds)
+                        tone_period=args.tone_period, seed=seed, min_seeds=args.min_seeds, blend=blend, blend_sweeps=args.blend_sweeps)
     make_pairs = lambda: synthetic_pairs(args.synthetic, *args.synthetic_size) if args.synthetic else folder_pairs(args.raw_folder, args.clean_folder)
     eraser = make(args.seed)
     res = T.evaluate_eraser(eraser, make_pairs(), T.EraserMetrics(args.brightness_difference, args.truth_dilate, ssim=args.ssim))
@@ -141,6 +144,9 @@ def eraser_main(args):
         plain = T.evaluate_eraser(make(None), make_pairs(), T.EraserMetrics(args.brightness_difference, args.truth_dilate))
         res.update(seed=args.seed, min_seeds=args.min_seeds, seed_dropped=eraser.dropped, seed_dropped_pixels=eraser.dropped_pixels,
                    without_seed=plain["mask"])
+    if args.blend:
+        plain = T.evaluate_eraser(make(args.seed, blend=False), make_pairs(), T.EraserMetrics(args.brightness_difference, args.truth_dilate))
+        res.update(blend=True, blend_sweeps=args.blend_sweeps, without_blend={"fill": plain["fill"], "routes": plain["routes"]})
     pages = [dict(sums=[int(v) for v in p["page"]], regions=len(p["rows"]), **({"ssim": p["ssim"]} if "ssim" in p else {})) for p in res.pop("pages")]
     line = {"task": "eraser", "seg_model": args.seg_model, "fill_model": "HarmonicFill" if args.filler == "harmonic" else args.fill_model,
             "pages": len(pages), **res, "per_page": pages}
@@ -186,6 +192,8 @@ def main(argv=None):
     ap.add_argument("--min-seeds", type=int, default=1, metavar="N")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"])
     ap.add_argument("--sweeps", type=int, default=8, metavar="N")
+    ap.add_argument("--blend", action="store_true", help="eraser: seamless composition of the filler's output; the line gains without_blend")
+    ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded synthetic images instead of a folder")
     ap.add_argument("--model", default=None, help="default: XceptionTextSegment / ImageFill")
     ap.add_argument("--checkpoint", default=None)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 18
+#define TSII_ABI_VERSION 19
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -995,6 +995,30 @@ int tsii_page_scores(const uint8_t* out, const uint8_t* clean, const uint8_t* ma
 size_t tsii_region_seeds_ws_bytes(int h, int w, int max_regions);
 int tsii_region_seeds(uint8_t* text, int* labels, const uint8_t* seed, int h, int w, int* table, int* n_regions, int max_regions,
                       int min_seeds, int tile, int halo, int* core_count, int* seeds, int* members, int* dropped, void* ws, void* stream);
+
+/* ---- K20: seamless fill (csrc/blend.hip) -- the output of an inpainting filler taken into the image in the gradient domain ("seamless",
+ * Poisson composition): inside a hole the result keeps the filler's gradients and takes its level from the valid pixels around the hole.
+ * That is the filler's output plus the harmonic continuation of its own error on the valid pixels (the membrane correction), and the
+ * harmonic continuation is tsii_harmonic_fill (K14).  Per image; the 3 channels share one validity plane.
+ * Inputs: x fp32 NHWC [n,h,w,3], the image as the filler saw it (what tsii_page_tiles_fill / tsii_page_windows_fill write); out fp32 NHWC
+ * [n,h,w,3], the filler's output; mask fp32 [n,h,w], a pixel is VALID iff mask != 0 (K14's plane); sweeps 0..16.  Output: dst fp32 NHWC
+ * [n,h,w,3]; it may be out itself (in place), never x.
+ *   1. o = min(max(out, 0), 1) at every pixel: the clamp of tsii_compose_page_u8, so that what is corrected is what the page would show.
+ *   2. d = x - o on the VALID pixels (one fp32 subtraction).  d under a hole is never used.
+ *   3. c = tsii_harmonic_fill(d, mask, sweeps): K14's semantics exactly as stated above (levels, apex, coarse to fine, the fixed order of
+ *      every mean).  An image without a valid pixel gets c = 0.
+ *   4. dst = out, bit for bit and not clamped, on the VALID pixels; dst = o + c (one fp32 addition, not clamped: compose clamps) on the
+ *      hole pixels.
+ *   5. The value of x at a hole pixel is NEVER USED (it may be NaN); out is read everywhere.
+ * The same bits on every run; an image of a batch equals the same image run alone.  No atomics, no allocation, no host synchronisation,
+ * everything on the caller's stream.
+ * ws: tsii_seamless_fill_ws_bytes(n, h, w) bytes (0: geometry refused; d, c and K14's own workspace, about 2.4 of x), 4-byte aligned (16
+ * for the vector paths); needs nothing cleared beforehand and holds nothing a later call depends on.
+ * Refused (non-zero return, tsii_last_error, nothing launched): n, h or w < 1; n*h*w*3 > 2^31; sweeps outside 0..16; a NULL among x, out,
+ * mask, dst, ws; dst == x. */
+size_t tsii_seamless_fill_ws_bytes(int n, int h, int w);
+int tsii_seamless_fill(const float* x, const float* out, const float* mask, int n, int h, int w, int sweeps, float* dst, void* ws,
+                       void* stream);
 
 #ifdef __cplusplus
 }

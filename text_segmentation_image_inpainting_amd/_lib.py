@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 18         # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 19         # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -189,6 +189,9 @@ SIGNATURES = {
     # K19 seeded regions (csrc/seeds.hip): text / labels / table in place behind K10 or K15, a uint8 seed plane, int32 seeds / members / dropped
     "tsii_region_seeds_ws_bytes": (_z, [_i, _i, _i]),
     "tsii_region_seeds": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p, _p]),
+    # K20 seamless fill (csrc/blend.hip): fp32 NHWC image and filler output, K14's validity plane; dst may be out
+    "tsii_seamless_fill_ws_bytes": (_z, [_i, _i, _i]),
+    "tsii_seamless_fill": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 _LIB = None

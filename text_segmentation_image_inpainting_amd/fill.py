@@ -9,6 +9,12 @@ background (a gradient, a soft shadow, a sky) and needs no inpainting checkpoint
 
 ``HarmonicFill`` obeys the ``filler`` calling convention of ``TextEraser``; ``harmonic_fill`` is the stand-alone form for a uint8 page
 and a mask.  Device tensors only: there is no CPU path.
+
+The same solver carries the seamless composition of ANOTHER filler's output (``csrc/blend.hip``, "K20: seamless fill"): an inpainting net
+reproduces structure well and absolute level badly, and its error at the valid pixels around a hole, continued harmonically into the hole
+and added there, takes the level of the patch back to that of its surroundings (Poisson cloning of the net's output into the page).
+``SeamlessFill(filler)`` wraps any filler, ``seamless_fill`` is the stand-alone form for a page, somebody's fill of it and a mask, and
+``TextEraser(blend=True)`` runs it between the filler and compose.
 """
 import numpy as np
 import torch
@@ -40,6 +46,24 @@ def _harmonic_fill(x_nhwc, plane, sweeps):
     ws = ops._ws(nbytes, x_nhwc)
     call("tsii_harmonic_fill", ptr(x_nhwc), ptr(plane), n, h, w, int(sweeps), ptr(out), ptr(ws), _lib.stream())
     return out
+
+
+def _seamless_fill(x_nhwc, out_nhwc, plane, sweeps):
+    """fp32 NHWC ``[n, h, w, 3]`` twice -- the image as the filler saw it and the filler's output -- and the validity plane fp32
+    ``[n, h, w]`` (valid iff != 0) -> the blended output, a new fp32 NHWC tensor (``tsii_seamless_fill``): ``out_nhwc`` bit for bit on the
+    valid pixels, its clamped value plus the harmonic continuation of ``x - clamp(out)`` under the holes; what ``x_nhwc`` holds under a
+    hole is never read"""
+    n, h, w, c = (int(v) for v in x_nhwc.shape)
+    assert c == 3 and tuple(out_nhwc.shape) == (n, h, w, 3) and tuple(plane.shape) == (n, h, w)
+    _lib.check_device(x_nhwc, out_nhwc, plane)
+    assert x_nhwc.device == out_nhwc.device == plane.device and x_nhwc.is_contiguous() and out_nhwc.is_contiguous() and plane.is_contiguous()
+    nbytes = int(_lib.lib().tsii_seamless_fill_ws_bytes(n, h, w))
+    if nbytes == 0:
+        raise ValueError(f"seamless fill: {n} images of {h} x {w} pixels (every extent >= 1, at most 2^31 elements)")
+    dst = torch.empty_like(out_nhwc)
+    ws = ops._ws(nbytes, x_nhwc)
+    call("tsii_seamless_fill", ptr(x_nhwc), ptr(out_nhwc), ptr(plane), n, h, w, int(sweeps), ptr(dst), ptr(ws), _lib.stream())
+    return dst
 
 
 def _validity_plane(mask, n, h, w):
@@ -89,6 +113,71 @@ class HarmonicFill:
 
     def __repr__(self):
         return f"HarmonicFill(sweeps={self.sweeps})"
+
+
+class SeamlessFill:
+    """``out[N,3,H,W] = SeamlessFill(filler, sweeps=8)((x[N,3,H,W], mask))``: ``filler`` -- anything that obeys the ``filler`` calling
+    convention of ``TextEraser`` -- with its output taken into ``x`` in the gradient domain (``tsii_seamless_fill``, "K20: seamless fill").
+    The inner filler is called with the same pair; where ``mask`` is 1 (non-zero) its output comes back bit for bit, over the holes its
+    output clamped to [0, 1] plus the harmonic continuation (``sweeps`` 0..16, as ``HarmonicFill``) of its own error ``x - clamp(out)`` on
+    the valid pixels: the gradients of the filler, the level of the surroundings.  ``mask`` in the forms ``HarmonicFill`` accepts; what
+    ``x`` holds under a hole reaches the inner filler only.  The result is the NCHW-shaped view of an NHWC tensor.
+    ``TextEraser(segmenter, filler, blend=True)`` is ``TextEraser(segmenter, SeamlessFill(filler))`` without the wrapper."""
+
+    def __init__(self, filler, sweeps=8):
+        if not callable(filler):
+            raise TypeError("filler must be callable: (x[N,3,H,W], mask) -> out[N,3,H,W]")
+        self.filler, self.sweeps = filler, check_sweeps(sweeps)
+
+    def __call__(self, args):
+        x, mask = args
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"x must be [N,3,H,W], got {tuple(getattr(x, 'shape', ()))}")
+        n, _, h, w = (int(v) for v in x.shape)
+        plane = _validity_plane(mask, n, h, w)
+        out = self.filler((x, mask))
+        if not isinstance(out, torch.Tensor) or tuple(out.shape) != (n, 3, h, w):
+            raise ValueError(f"filler returned {tuple(getattr(out, 'shape', ()))} for x {tuple(x.shape)}")
+        nhwc = lambda t: t.float().permute(0, 2, 3, 1).contiguous()
+        return _seamless_fill(nhwc(x), nhwc(out), plane, self.sweeps).permute(0, 3, 1, 2)
+
+    def __repr__(self):
+        return f"SeamlessFill({self.filler!r}, sweeps={self.sweeps})"
+
+
+def _page_and_plane(page_u8, mask_u8, what="page"):
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    m = torch.from_numpy(np.ascontiguousarray(mask_u8)) if isinstance(mask_u8, np.ndarray) else mask_u8
+    if not isinstance(p, torch.Tensor) or p.dim() != 3 or p.shape[2] != 3 or p.dtype != torch.uint8 or p.shape[0] < 1 or p.shape[1] < 1:
+        raise ValueError(f"{what} must be [H, W, 3] uint8, got {tuple(getattr(p, 'shape', ()))} {getattr(p, 'dtype', type(p))}")
+    if not isinstance(m, torch.Tensor) or m.dtype != torch.uint8 or tuple(m.shape) != tuple(p.shape[:2]):
+        raise ValueError(f"mask must be [H, W] uint8 for a page of {tuple(p.shape)}, got {tuple(getattr(m, 'shape', ()))} "
+                         f"{getattr(m, 'dtype', type(m))}")
+    return p, m
+
+
+def seamless_fill(page_u8, fill_u8, mask_u8, sweeps=8, device=None):
+    """``clean_u8``: ``page_u8`` with the pixels under the mask taken from ``fill_u8`` -- the output of any inpainter, on the page's grid --
+    in the gradient domain: the fill's gradients, the level of the page around each hole.  ``page_u8`` and ``fill_u8``: ``[H, W, 3]``
+    uint8 of any size; ``mask_u8``: ``[H, W]`` uint8, non-zero = replaced; numpy or torch, none is modified.  One call of the kernel
+    (``tsii_seamless_fill``) on the whole page with ``x = page / 255`` and ``out = fill / 255``.  Pixels outside the mask come back byte for
+    byte; inside, ``floor(clamp(v, 0, 1) * 255 + 0.5)`` of the blended value, the compose kernels' rounding.  The result is the same
+    kind (and on the same device) as ``page_u8``; host arguments are computed on ``device`` (default ``cuda:0``)."""
+    sweeps = check_sweeps(sweeps)
+    p, m = _page_and_plane(page_u8, mask_u8)
+    f = torch.from_numpy(np.ascontiguousarray(fill_u8)) if isinstance(fill_u8, np.ndarray) else fill_u8
+    if not isinstance(f, torch.Tensor) or f.dtype != torch.uint8 or tuple(f.shape) != tuple(p.shape):
+        raise ValueError(f"fill must be [H, W, 3] uint8 like the page {tuple(p.shape)}, got {tuple(getattr(f, 'shape', ()))} "
+                         f"{getattr(f, 'dtype', type(f))}")
+    dev = torch.device(device) if device is not None else (p.device if p.is_cuda else torch.device("cuda:0"))
+    page, fill, hole = p.to(dev).contiguous(), f.to(dev).contiguous(), m.to(dev) != 0
+    x, out = (page.float() / 255.0).unsqueeze(0), (fill.float() / 255.0).unsqueeze(0)
+    blended = _seamless_fill(x, out, (~hole).float().unsqueeze(0), sweeps)[0]
+    rounded = torch.floor(blended.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+    clean = torch.where(hole.unsqueeze(-1), rounded, page)
+    if isinstance(page_u8, np.ndarray):
+        return clean.cpu().numpy()
+    return clean if clean.device == page_u8.device else clean.to(page_u8.device)
 
 
 def harmonic_fill(page_u8, mask_u8, sweeps=8, device=None):

@@ -31,6 +31,10 @@ filter, the hulls, the flat stage and ``pack`` then judge, fill, paint and place
 With ``seed`` the one cut at ``threshold`` becomes a hysteresis threshold: a region (with ``group``: a block) stays text only if the
 segmenter was sure, at the probability ``seed``, somewhere inside it (``csrc/seeds.hip``; "K19: seeded regions").  What is dropped leaves the
 plane, the labels and the table on the device, in front of the hulls, the routes and the page's one synchronisation.
+
+With ``blend`` the pixels the filler paints are taken into the page in the gradient domain (``csrc/blend.hip``; "K20: seamless fill", around
+the solver of ``csrc/harmonic.hip``): the filler's error at the valid pixels of each tile, continued harmonically into the holes, is added
+there between the filler and compose.
 """
 from contextlib import contextmanager
 from dataclasses import dataclass
@@ -43,6 +47,7 @@ from torch import nn
 from . import _lib
 from ._lib import call, ptr
 from .BaseModels import to_nhwc
+from .fill import _seamless_fill, check_sweeps
 from .masks import MaskParts
 from .regions import (ReadBack, _flat_regions, _region_hulls, _region_seeds, _smooth_regions, _text_blocks, _text_regions, _tone_regions,
                       check_block_args, check_flat_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
@@ -288,7 +293,7 @@ def _eval_mode(*nets):
 # yet), "joined" (the read-back tensor is formed; "counts_d2h" behind it is the copy alone) and "planned" (the host has selected the
 # tiles or planned the windows and uploaded their small index tensors).
 STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "seeds", "hulls",
-               "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler",
+               "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
                "compose_page_u8", "compose_page_windows_u8", "download")
 
 
@@ -403,6 +408,19 @@ class TextEraser:
     ``evaluate_eraser`` on raw / clean pairs: the mask's precision and recall with and without it.  Still one synchronisation.  ``None``
     (the default): none of this runs.
 
+    ``blend=True``: seamless (gradient-domain, Poisson) composition of what the filler paints.  An inpainting net reproduces structure well
+    and absolute level badly: its patch is plausible and a shade lighter or darker than the page around it.  The filler returns the whole
+    tile, so its error ``x - clamp(out, 0, 1)`` is known at the valid pixels around every hole; between the filler and compose the harmonic
+    continuation of that error into the holes (``blend_sweeps`` 0..16 sweeps per level, the solver of ``HarmonicFill``) is added to the
+    filler's clamped output there, on the device, for all tiles or windows in one call: the filler's gradients, the page's level --
+    ``TextEraser(segmenter, SeamlessFill(filler, blend_sweeps))``, byte for byte, on the grid and with ``pack``.  A filler whose error is
+    one constant comes back exact; ``HarmonicFill`` is left as it is (it has no error at the valid pixels).  The limits: the correction
+    is per tile -- a hole across two cores is corrected by each tile from its own window, so the two halves may meet at slightly
+    different levels; it interpolates the filler's error at the ring, so noise there is spread smoothly a few pixels into the hole; a
+    tile without a valid pixel is not corrected.  Whether it helps a given checkpoint is for ``evaluate_eraser`` on raw / clean pairs to
+    say (the ``fill`` and ``routes["net"]`` rows).  ``last_stats`` gains ``blended``, the tiles or windows that went through it.  Still one
+    synchronisation.  ``False`` (the default): none of this runs.
+
     The page is ``[H, W, 3]`` uint8, numpy or torch, host or device, any ``H, W >= 1``; the results come back the same kind, on
     the same device.  A list of pages gives a list of ``(clean, mask)`` pairs.  ``mask`` is ``[H, W]`` uint8, 255 = text;
     ``clean`` equals the page wherever ``mask`` is 0.
@@ -411,7 +429,7 @@ class TextEraser:
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
                  max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
-                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1):
+                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1, blend=False, blend_sweeps=8):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -445,6 +463,9 @@ class TextEraser:
         check_seed_args(min_seeds)
         self.seed, self.min_seeds = None if seed is None else float(seed), int(min_seeds)
         self.seed_logit = None if seed is None else logit_of(seed)
+        if blend or blend_sweeps != 8:
+            check_sweeps(blend_sweeps)
+        self.blend, self.blend_sweeps = bool(blend), int(blend_sweeps)
         self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
                         or self.seed is not None)
         self.segmenter, self.filler = segmenter, filler
@@ -639,6 +660,10 @@ class TextEraser:
         if where is not None:
             out = self._run_filler(img, mplane, g)
         self._mark("filler")
+        if self.blend:                                  # the filler's error at the valid pixels, continued into the holes and added there
+            if out is not None:
+                out = _seamless_fill(img, out, mplane, self.blend_sweeps)
+            self._mark("blend")
         clean = st.both[:h * w * 3].view(h, w, 3)
         if windows is None:
             _compose_page_u8(st.src, st.text, out, None if where is None else where[1], g, clean, st.compose_mask)
@@ -654,6 +679,8 @@ class TextEraser:
         if self.group is not None:
             self.last_stats.update(blocks=read.kept)
         self.last_stats.update(route_stats)
+        if self.blend:
+            self.last_stats.update(blended=self.last_stats["selected"])
         if self.seed is not None:
             self.last_stats.update(seed_dropped=read.seed_dropped, seed_dropped_pixels=read.seed_dropped_pixels)
         if self.pack:

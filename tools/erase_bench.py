@@ -4,6 +4,7 @@
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
                                 [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
                                 [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T] [--tones SHARE] [--tone T [--tone-ring N] [--tone-period N]]
+                                [--blend [--blend-sweeps N]]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  The tool has no copy of the page's course: it puts a recorder in the place of ``TextEraser._mark``
@@ -58,6 +59,12 @@ reports ``components`` and ``largest_block`` (members).  Compare with the same l
 with ``--seg-long-side`` -- then tsii_region_seeds, behind the regions / blocks stages) with its own pair of events; ``regions`` then reports
 ``seed_dropped`` / ``seed_dropped_pixels``.  ``--faint SHARE`` gives that share of the blobs a logit of 1 (a probability of 0.73) instead of
 4, so that a ``P`` between the two has something to drop.  Compare with the same line without ``--seed`` in the same session.
+
+``--blend`` adds the ``blend`` stage (tsii_seamless_fill on the filler's tiles or windows, between the filler and compose) with its own pair
+of events.  Compare with the same line without ``--blend`` in the same session, and with ``--filler harmonic``, whose filler stage is the
+stage's solver on the same tiles, ``tile_batch`` at a time and with the filler's gather.  ``blend_split_ms`` is the direct comparison: on
+the tiles (or windows) the run sent, with their own hole planes, ``tsii_harmonic_fill`` alone and ``tsii_seamless_fill`` in one call each,
+HIP events around the call: the difference is what the residual and apply passes add.
 """
 import argparse
 import json
@@ -160,6 +167,8 @@ def main(argv=None):
     ap.add_argument("--faint", type=float, default=0.0, metavar="SHARE", help="this share of the blobs has a logit of 1 instead of 4")
     ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
     ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
+    ap.add_argument("--blend", action="store_true", help="time the blend stage (tsii_seamless_fill) between the filler and compose")
+    ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --blend (0..16)")
     args = ap.parse_args(argv)
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
@@ -203,7 +212,8 @@ def main(argv=None):
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
                           flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth, tone=args.tone,
-                          tone_ring=args.tone_ring, tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds)
+                          tone_ring=args.tone_ring, tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend,
+                          blend_sweeps=args.blend_sweeps)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -254,7 +264,7 @@ def main(argv=None):
                 region_info.update(labelled=len(read.route_table))
                 region_info.update({name + s: stats[name + s] for name in read.stages for s in ("_regions", "_pixels")})
         return (rec.stage_ms(), int((read.counts > 0).sum()), int(read.counts.sum()), st, int(st.read_back.numel()), region_info,
-                planned["windows"], planned["ms"])
+                planned["windows"], planned["ms"], read.counts)
 
     for _ in range(args.warmup):
         one_page()
@@ -303,6 +313,8 @@ def main(argv=None):
         chunks = -(-((args.tone_period + 1) * (2 * args.tone_period + 1)) // 128)
         apron = (64 + 2 * args.tone_ring) * (32 + 2 * args.tone_ring) / 2048.0
         bytes_["tone"] = int(chunks * apron * npx) + npx + 9 * npx + 16 * int(runs[0][5]["tone_pixels"] + n_text)
+    if args.blend:                          # DESIGN.md, "seamless fill", per tile pixel: residual 12 + 12 + 4 in, 12 out; the solver 2.1 x (12 + 4) in
+        bytes_["blend"] = int((40 + 2.1 * 16 + 12 + 40) * n_fill * tpx)     # + 12 out; apply 12 + 12 + 4 in, 12 out
 
     def timed(fn, sync=True):
         for _ in range(args.warmup):
@@ -365,6 +377,32 @@ def main(argv=None):
             return up[0, 0].to(torch.uint8).to(dev)
         host_resample = {"resize": timed(host_resize), "plane_up": timed(host_plane_up)}
 
+    blend_split = None
+    if args.blend and n_fill > 0:                           # the run's own tiles or windows: the solver alone against the whole call
+        from text_segmentation_image_inpainting_amd.fill import _harmonic_fill, _seamless_fill
+        if windows is None:
+            ids = torch.tensor([t for t in range(g.count) if runs[0][8][t] > 0], dtype=torch.int32, device=dev)
+            img, mplane = P._page_tiles_fill(state.src, state.text, g, ids)
+        else:
+            img, mplane = P._page_windows_fill(state.src, state.text, g, torch.from_numpy(windows[0]).to(dev))
+        net_out = torch.rand_like(img) * 1.2 - 0.1
+
+        def events_ms(fn):
+            for _ in range(args.warmup):
+                fn()
+            vals = []
+            for _ in range(args.repeats):
+                torch.cuda.synchronize()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                torch.cuda.synchronize()
+                vals.append(e0.elapsed_time(e1))
+            return {"median": round(statistics.median(vals), 4), "min": round(min(vals), 4), "max": round(max(vals), 4)}
+        blend_split = {"tiles": int(img.shape[0]), "harmonic_fill_alone": events_ms(lambda: _harmonic_fill(img, mplane, args.blend_sweeps)),
+                       "seamless_fill": events_ms(lambda: _seamless_fill(img, net_out, mplane, args.blend_sweeps))}
+
     host_route = None
     if with_regions:
         text0, _ = P._tiles_text_mask(logits_fixed, g, eraser.logit_threshold, args.dilate)      # the plane before the filter
@@ -425,6 +463,7 @@ def main(argv=None):
         "ramps": args.ramps, "smooth": args.smooth, "smooth_split_ms": smooth_split,
         "tones": args.tones, "tone": args.tone, "tone_ring": args.tone_ring if with_tone else None,
         "tone_period": args.tone_period if with_tone else None,
+        "blend": args.blend, "blend_sweeps": args.blend_sweeps if args.blend else None, "blend_split_ms": blend_split,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
