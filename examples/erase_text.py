@@ -32,6 +32,10 @@ by copying the pixel a whole number of periods away, behind ``--smooth``.  The p
 ``--filler harmonic`` needs no inpainting checkpoint: the holes take the smooth continuation of their surroundings (``T.HarmonicFill``,
 ``--sweeps N`` Jacobi sweeps per level, default 8), the right fill for text on a gradient, a soft shadow or a sky; no inpainting net is
 built or loaded.
+``--filler patch`` needs none either and continues what runs UNDER the text -- a panel border, an outline, hatching, screentone of any pitch
+-- with the page's own pixels (``T.PatchFill``: every hole pixel is a copy of a pixel of its tile whose ``--patch N`` x N window, odd 3..9,
+default 7, matches; ``--levels N`` pyramid levels, ``--iters N`` search iterations per level, ``--fill-seed S``; the first guess is the
+harmonic fill with ``--sweeps``).  It cannot draw what the tile does not contain.
 ``--blend`` takes what the inpainting net paints into the page in the gradient domain (seamless, Poisson composition): the net's own error at
 the pixels around every hole, continued harmonically into the hole (``--blend-sweeps N`` Jacobi sweeps per level, default 8) and added
 there, so that a patch whose content is right and whose level is a shade off no longer stands out.  Per tile, on the device, between the
@@ -95,8 +99,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=float, default=None, metavar="P", help="keep a text region only if some pixel of it has a text probability above P "
                     "(--threshold <= P < 1): a hysteresis threshold")
     ap.add_argument("--min-seeds", type=int, default=1, metavar="N", help="the pixels above --seed a region needs to stay")
-    ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: fill the holes with T.HarmonicFill, without an inpainting net")
-    ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
+    ap.add_argument("--filler", default="net", choices=["net", "harmonic", "patch"], help="harmonic: fill the holes with T.HarmonicFill, patch: with "
+                    "T.PatchFill (copies of page pixels); neither needs an inpainting net")
+    ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic and of the first guess of --filler patch (0..16)")
+    ap.add_argument("--patch", type=int, default=7, metavar="N", help="window of --filler patch: odd, 3..9")
+    ap.add_argument("--levels", type=int, default=4, metavar="N", help="pyramid levels of --filler patch (1..6)")
+    ap.add_argument("--iters", type=int, default=4, metavar="N", help="search iterations per level of --filler patch (1..8)")
+    ap.add_argument("--fill-seed", type=int, default=0, metavar="S", help="seed of the random search of --filler patch (32 bits)")
     ap.add_argument("--blend", action="store_true", help="seamless composition: correct the level of what the filler paints from its error around the holes")
     ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --blend (0..16)")
     args = ap.parse_args(argv)
@@ -105,8 +114,9 @@ def main(argv=None):
     torch.manual_seed(0)
     nets = []
     for name, ckpt in ((args.seg_model, args.seg_checkpoint), (args.fill_model, args.fill_checkpoint)):
-        if len(nets) == 1 and args.filler == "harmonic":
-            nets.append(T.HarmonicFill(args.sweeps))                       # a kernel, not a net: nothing to build or load
+        if len(nets) == 1 and args.filler != "net":                        # kernels, not a net: nothing to build or load
+            nets.append(T.HarmonicFill(args.sweeps) if args.filler == "harmonic" else
+                        T.PatchFill(args.patch, args.levels, args.iters, args.fill_seed, args.sweeps))
             break
         net = getattr(T, name)()
         if ckpt:

@@ -114,6 +114,8 @@ def eraser_main(args):
         seg.load_state_dict(torch.load(args.seg_checkpoint, map_location="cpu"))
     if args.filler == "harmonic":
         fill = T.HarmonicFill(args.sweeps)
+    elif args.filler == "patch":
+        fill = T.PatchFill(args.patch, args.levels, args.iters, args.fill_seed, args.sweeps)
     else:
         fill = getattr(T, args.fill_model)()
         if args.fill_checkpoint:
@@ -148,7 +150,7 @@ def eraser_main(args):
         plain = T.evaluate_eraser(make(args.seed, blend=False), make_pairs(), T.EraserMetrics(args.brightness_difference, args.truth_dilate))
         res.update(blend=True, blend_sweeps=args.blend_sweeps, without_blend={"fill": plain["fill"], "routes": plain["routes"]})
     pages = [dict(sums=[int(v) for v in p["page"]], regions=len(p["rows"]), **({"ssim": p["ssim"]} if "ssim" in p else {})) for p in res.pop("pages")]
-    line = {"task": "eraser", "seg_model": args.seg_model, "fill_model": "HarmonicFill" if args.filler == "harmonic" else args.fill_model,
+    line = {"task": "eraser", "seg_model": args.seg_model, "fill_model": {"harmonic": "HarmonicFill", "patch": repr(fill)}.get(args.filler, args.fill_model),
             "pages": len(pages), **res, "per_page": pages}
     line = strict_json(line)
     print(json.dumps(line, allow_nan=False))
@@ -190,8 +192,12 @@ def main(argv=None):
     ap.add_argument("--group", type=int, default=None, metavar="G")
     ap.add_argument("--seed", type=float, default=None, metavar="P", help="eraser: keep a text region only if some pixel of it has a probability above P")
     ap.add_argument("--min-seeds", type=int, default=1, metavar="N")
-    ap.add_argument("--filler", default="net", choices=["net", "harmonic"])
+    ap.add_argument("--filler", default="net", choices=["net", "harmonic", "patch"])
     ap.add_argument("--sweeps", type=int, default=8, metavar="N")
+    ap.add_argument("--patch", type=int, default=7, metavar="N")
+    ap.add_argument("--levels", type=int, default=4, metavar="N")
+    ap.add_argument("--iters", type=int, default=4, metavar="N")
+    ap.add_argument("--fill-seed", type=int, default=0, metavar="S")
     ap.add_argument("--blend", action="store_true", help="eraser: seamless composition of the filler's output; the line gains without_blend")
     ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N")
     ap.add_argument("--synthetic", type=int, default=0, metavar="N", help="N seeded synthetic images instead of a folder")

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 19
+#define TSII_ABI_VERSION 20
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -1019,6 +1019,52 @@ int tsii_region_seeds(uint8_t* text, int* labels, const uint8_t* seed, int h, in
 size_t tsii_seamless_fill_ws_bytes(int n, int h, int w);
 int tsii_seamless_fill(const float* x, const float* out, const float* mask, int n, int h, int w, int sweeps, float* dst, void* ws,
                        void* stream);
+
+/* ---- K21: patch fill (csrc/patch.hip) -- exemplar-based fill: every hole pixel becomes a COPY of a page pixel whose (2r+1)^2 neighbourhood
+ * matches the hole pixel's own, found by a PatchMatch-style search of a nearest-neighbour field, coarse to fine.  Per image; every operation
+ * is an integer operation, so every run gives the same bits and an image of a batch equals the same image run alone.
+ * Inputs: page uint8 [n,h,w,3]; hole uint8 [n,h,w], a pixel is a HOLE iff hole != 0; init uint8 [n,h,w,3], a first guess of the hole
+ * pixels (a harmonic fill, say; any bytes are legal); radius r 1..4; levels 1..6; iters 1..8; seed, any 32 bits.  Outputs: out uint8
+ * [n,h,w,3] (it may be init, never page); nnf int32 [n,h,w,2]; stats int32 [n,3].
+ *   Levels.  h_0 = h, w_0 = w, h_{l+1} = (h_l + 1) / 2, w_{l+1} = (w_l + 1) / 2.  L = min(levels, the number of l with min(h_l, w_l) >=
+ *     2r+1), at least 1: levels 0 .. L-1 are used.
+ *   Work image.  W_0[p] = init[p] where p is a hole, page[p] elsewhere: the value of page under a hole is NEVER USED, init is used under
+ *     the holes only.  H_0[p] = (hole[p] != 0).  The children of a pixel (Y, X) of level l+1 are the pixels (2Y + a, 2X + b), a, b in {0, 1},
+ *     that lie on level l; cnt is their number (1, 2 or 4).  W_{l+1}[Y,X][c] = (sum of W_l[child][c] + cnt / 2) / cnt (integer division),
+ *     holes and valid pixels alike; H_{l+1}[Y,X] = some child is a hole.
+ *   Admissible.  A pixel s of level l is an admissible SOURCE iff all (2r+1)^2 pixels s + d, |d|_inf <= r, lie on the level and none of them
+ *     is a hole.
+ *   Field.  NNF_l[p], for the hole pixels p of level l, is an admissible source or "none"; p is SOURCED iff it is not none.  At level L-1
+ *     the field starts as none everywhere.  At a level l < L-1 it starts from the final field of level l+1: with P = (y >> 1, x >> 1) the
+ *     parent of p = (y, x), none if P is not sourced, else c = (2 sy + (y & 1), 2 sx + (x & 1)) for (sy, sx) = NNF_{l+1}[P] if c is
+ *     admissible at level l, else none.
+ *   Cost.  T[q] = W_l[NNF_l[q]] if q is a sourced hole pixel, W_l[q] otherwise.  cost(p, s) = the sum over the d with |d|_inf <= r and p + d
+ *     on the level, and over the 3 channels c, of |T[p + d][c] - W_l[s + d][c]|.
+ *   Iteration t = 1 .. iters of level l (Jacobi: the field F read -- in T, as the current source and by propagation -- is the one after
+ *     iteration t-1, all new values go to a second field).  For every hole pixel p = (y, x), the candidates are
+ *       a. F[p], if p is sourced;
+ *       b. propagation, jump-flooded: for k in {1, 2, 4, 8} and e in {(0,1), (0,-1), (1,0), (-1,0)}: if q = p + k e lies on the level and is
+ *          a sourced hole pixel, F[q] - k e;
+ *       c. random search around centre = F[p] if p is sourced, else p: for j = 0, 1, ... with R_j = max(h_l, w_l) >> j while R_j >= 1, the
+ *          pixel centre + (oy, ox), m = 2 R_j + 1, u = hash(seed, l, t, y, x, j),
+ *          oy = (int)(((uint64)(u & 0xffff) * m) >> 16) - R_j,  ox = (int)(((uint64)(u >> 16) * m) >> 16) - R_j  (both in [-R_j, R_j]).
+ *     Candidates that are not admissible (off the level included) are dropped.  The new F[p] is the candidate with the smallest
+ *     (cost, sy, sx), lexicographically; none if no candidate is left.
+ *   Hash (all uint32, wrapping).  mix(v): v ^= v >> 16; v *= 0x7feb352d; v ^= v >> 15; v *= 0x846ca68b; v ^= v >> 16.
+ *     hash = mix(mix(mix(mix(seed + 0x9e3779b9 * (16 l + t)) ^ y) ^ x) ^ (0x9e3779b9 * (j + 1))).  The image index is not hashed.
+ *   Result, from NNF_0 after the last iteration.  Valid pixel: out = page byte for byte, nnf = (-1, -1).  Sourced hole pixel: nnf = (sy,
+ *     sx), out = page[sy, sx], the bytes of a page pixel that is not a hole.  Hole pixel without a source (no admissible source on the
+ *     level, or none was met): out = init, nnf = (-1, -1).  stats[i] = (holes, sourced, holes - sourced) of image i.
+ * Integer sums only (the counts of stats are accumulated with integer atomics, whose order changes nothing); no allocation, no host
+ * synchronisation, everything on the caller's stream.
+ * ws: tsii_patch_fill_ws_bytes(n, h, w, radius, levels) bytes (0: refused; per used level a packed RGBX word, two field words and two flag
+ * bytes per pixel: about 17 bytes per page pixel), 4-byte aligned (16 for the vector paths); needs nothing cleared beforehand and holds
+ * nothing a later call depends on.
+ * Refused (non-zero return, tsii_last_error, nothing launched): n, h or w < 1; n*h*w*3 >= 2^31; radius outside 1..4; levels outside 1..6;
+ * iters outside 1..8; a NULL among page, hole, init, out, nnf, stats, ws; out == page. */
+size_t tsii_patch_fill_ws_bytes(int n, int h, int w, int radius, int levels);
+int tsii_patch_fill(const uint8_t* page, const uint8_t* hole, const uint8_t* init, int n, int h, int w, int radius, int levels, int iters,
+                    uint32_t seed, uint8_t* out, int32_t* nnf, int32_t* stats, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -16,6 +16,6 @@ from .pipeline import TextEraser, plan_fill_windows, resize_page_u8, working_siz
 from .regions import (FlatFill, RegionHulls, SeededRegions, SmoothFill, TextBlocks, TextRegions, ToneFill, check_tone_args,  # noqa: F401,E402
                       fill_region_hulls, flat_fill_regions, seeded_regions, smooth_fill_regions, text_blocks, text_regions,
                       tone_fill_regions)
-from .fill import HarmonicFill, SeamlessFill, harmonic_fill, seamless_fill  # noqa: F401,E402
+from .fill import HarmonicFill, PatchFill, SeamlessFill, harmonic_fill, patch_fill, seamless_fill  # noqa: F401,E402
 from .metrics import InpaintingMetrics, SegmentationMetrics, evaluate_inpainting, evaluate_segmentation  # noqa: F401,E402
 from .score import EraserMetrics, evaluate_eraser, pair_text_mask, score_page  # noqa: F401,E402

@@ -15,6 +15,11 @@ reproduces structure well and absolute level badly, and its error at the valid p
 and added there, takes the level of the patch back to that of its surroundings (Poisson cloning of the net's output into the page).
 ``SeamlessFill(filler)`` wraps any filler, ``seamless_fill`` is the stand-alone form for a page, somebody's fill of it and a mask, and
 ``TextEraser(blend=True)`` runs it between the filler and compose.
+
+Neither of the two invents texture.  ``PatchFill`` does (``csrc/patch.hip``, "K21: patch fill"): every hole pixel becomes a COPY of a page
+pixel whose neighbourhood matches the hole pixel's own -- an edge, hatching or screentone running under the text is continued with the
+page's own pixels -- found by a PatchMatch-style search of a nearest-neighbour field, coarse to fine, from the harmonic fill as the
+first guess.  ``patch_fill`` is the stand-alone form for a page and a mask.
 """
 import numpy as np
 import torch
@@ -24,12 +29,50 @@ from ._lib import call, ptr
 from .masks import MaskParts
 
 MAX_SWEEPS = 16                 # what tsii_harmonic_fill accepts (the LDS a block has for its patch and apron)
+MAX_PATCH, MAX_LEVELS, MAX_ITERS = 9, 6, 8      # what tsii_patch_fill accepts (radius 1..4)
 
 
 def check_sweeps(sweeps):
     if isinstance(sweeps, bool) or int(sweeps) != sweeps or not 0 <= sweeps <= MAX_SWEEPS:
         raise ValueError(f"sweeps {sweeps} must be an integer in 0..{MAX_SWEEPS}")
     return int(sweeps)
+
+
+def _check_int(name, v, lo, hi):
+    if isinstance(v, bool) or not isinstance(v, (int, np.integer)) or not lo <= v <= hi:
+        raise ValueError(f"{name} {v!r} must be an integer in {lo}..{hi}")
+    return int(v)
+
+
+def check_patch_args(patch, levels, iters, seed):
+    """-> (radius, levels, iters, seed) of ``tsii_patch_fill``: ``patch`` odd in 3..9, ``levels`` 1..6, ``iters`` 1..8, ``seed`` 32 bits"""
+    patch = _check_int("patch", patch, 3, MAX_PATCH)
+    if patch % 2 == 0:
+        raise ValueError(f"patch {patch} must be odd (3, 5, 7 or 9): the window is centred on its pixel")
+    return patch // 2, _check_int("levels", levels, 1, MAX_LEVELS), _check_int("iters", iters, 1, MAX_ITERS), _check_int("seed", seed, 0, 2 ** 32 - 1)
+
+
+def _patch_fill(page_u8_nhwc, hole_u8, init_u8, radius, levels, iters, seed):
+    """uint8 ``[n, h, w, 3]`` page, uint8 ``[n, h, w]`` hole plane (hole iff != 0) and uint8 ``[n, h, w, 3]`` first guess (read under the
+    holes only) -> ``(out uint8 [n, h, w, 3], nnf int32 [n, h, w, 2], stats int32 [n, 3])`` (``tsii_patch_fill``): device tensors, nothing
+    is read back; what the page holds under a hole is never used"""
+    n, h, w, c = (int(v) for v in page_u8_nhwc.shape)
+    assert c == 3 and tuple(hole_u8.shape) == (n, h, w) and tuple(init_u8.shape) == (n, h, w, 3)
+    assert page_u8_nhwc.dtype == hole_u8.dtype == init_u8.dtype == torch.uint8
+    _lib.check_device(page_u8_nhwc.new_empty(0, dtype=torch.float32))       # no CPU path: the byte planes' device goes into the check
+    assert page_u8_nhwc.device == hole_u8.device == init_u8.device
+    assert page_u8_nhwc.is_contiguous() and hole_u8.is_contiguous() and init_u8.is_contiguous()
+    nbytes = int(_lib.lib().tsii_patch_fill_ws_bytes(n, h, w, int(radius), int(levels)))
+    if nbytes == 0:
+        raise ValueError(f"patch fill: {n} images of {h} x {w} pixels (every extent >= 1, fewer than 2^31 elements), radius {radius} (1..4), "
+                         f"levels {levels} (1..{MAX_LEVELS})")
+    out = torch.empty_like(page_u8_nhwc)
+    nnf = torch.empty((n, h, w, 2), dtype=torch.int32, device=out.device)
+    stats = torch.empty((n, 3), dtype=torch.int32, device=out.device)
+    ws = ops._ws(nbytes, out)
+    call("tsii_patch_fill", ptr(page_u8_nhwc), ptr(hole_u8), ptr(init_u8), n, h, w, int(radius), int(levels), int(iters), int(seed), ptr(out),
+         ptr(nnf), ptr(stats), ptr(ws), _lib.stream())
+    return out, nnf, stats
 
 
 def _harmonic_fill(x_nhwc, plane, sweeps):
@@ -113,6 +156,43 @@ class HarmonicFill:
 
     def __repr__(self):
         return f"HarmonicFill(sweeps={self.sweeps})"
+
+
+def _quantise(t):
+    """fp32 in [0, 1] -> uint8, the compose kernels' rounding"""
+    return torch.floor(t.clamp(0.0, 1.0) * 255.0 + 0.5).to(torch.uint8)
+
+
+class PatchFill:
+    """``out[N,3,H,W] = PatchFill(patch=7, levels=4, iters=4, seed=0, sweeps=8)((x[N,3,H,W], mask))``: the ``filler`` of a ``TextEraser``
+    that continues what runs UNDER the text -- a panel border, an outline, hatching, screentone of any pitch -- with the page's own
+    pixels and without a net.  ``x`` is ``page / 255 * mask`` as ``TextEraser`` passes it (any fp32 in [0, 1] works: it is quantised with
+    ``floor(clamp(x, 0, 1) * 255 + 0.5)``), ``mask`` as for ``HarmonicFill``.  The first guess is ``HarmonicFill(sweeps)`` of the same pair;
+    ``tsii_patch_fill`` then searches, coarse to fine over ``levels`` levels and ``iters`` iterations each, for every hole pixel the
+    pixel of the same image whose ``patch x patch`` window (odd, 3..9; free of holes) matches the hole pixel's own best, and copies it.
+    Every output pixel under a hole is therefore a pixel ``x`` holds somewhere else (the harmonic value where an image has no window
+    without a hole); valid pixels come back as ``x`` quantised, which for a uint8 page over 255 is ``x`` bit for bit.  All integer: the
+    same bits on every run; another ``seed`` (32 bits) gives another, equally good, fill.  No synchronisation; the result is the
+    NCHW-shaped view of an NHWC tensor.  Not an ``nn.Module``: no parameters, nothing to load."""
+
+    def __init__(self, patch=7, levels=4, iters=4, seed=0, sweeps=8):
+        self.radius, self.levels, self.iters, self.seed = check_patch_args(patch, levels, iters, seed)
+        self.patch, self.sweeps = 2 * self.radius + 1, check_sweeps(sweeps)
+
+    def __call__(self, args):
+        x, mask = args
+        if not isinstance(x, torch.Tensor) or x.dim() != 4 or x.shape[1] != 3:
+            raise ValueError(f"x must be [N,3,H,W], got {tuple(getattr(x, 'shape', ()))}")
+        n, _, h, w = (int(v) for v in x.shape)
+        plane = _validity_plane(mask, n, h, w)
+        x_nhwc = x.float().permute(0, 2, 3, 1).contiguous()
+        init = _harmonic_fill(x_nhwc, plane, self.sweeps)
+        hole = (plane == 0).to(torch.uint8)
+        out, _, _ = _patch_fill(_quantise(x_nhwc), hole, _quantise(init), self.radius, self.levels, self.iters, self.seed)
+        return (out.float() / 255.0).permute(0, 3, 1, 2)
+
+    def __repr__(self):
+        return f"PatchFill(patch={self.patch}, levels={self.levels}, iters={self.iters}, seed={self.seed}, sweeps={self.sweeps})"
 
 
 class SeamlessFill:
@@ -202,3 +282,28 @@ def harmonic_fill(page_u8, mask_u8, sweeps=8, device=None):
     if isinstance(page_u8, np.ndarray):
         return clean.cpu().numpy()
     return clean if clean.device == page_u8.device else clean.to(page_u8.device)
+
+
+def patch_fill(page_u8, mask_u8, patch=7, levels=4, iters=4, seed=0, sweeps=8, return_field=False, device=None):
+    """``clean_u8``: the page with every pixel under the mask replaced by a COPY of a page pixel outside the mask whose ``patch x patch``
+    neighbourhood matches (``tsii_patch_fill`` from ``harmonic_fill(page_u8, mask_u8, sweeps)`` as the first guess; arguments as
+    ``PatchFill``).  ``page_u8``: ``[H, W, 3]`` uint8 of any size; ``mask_u8``: ``[H, W]`` uint8, non-zero = remove; numpy or torch,
+    neither is modified.  One call of the kernels on the whole page.  Pixels outside the mask come back byte for byte; a pixel under it
+    is the harmonic value only where the page has no window free of the mask.  ``return_field=True``: ``(clean_u8, nnf, stats)`` with
+    ``nnf`` int32 ``[H, W, 2]``, the ``(y, x)`` every masked pixel was copied from (-1, -1 elsewhere), and ``stats`` int32 ``[3]`` =
+    (masked, copied, masked - copied).  The results are the same kind (and on the same device) as ``page_u8``; host arguments are computed
+    on ``device`` (default ``cuda:0``)."""
+    radius, levels, iters, seed = check_patch_args(patch, levels, iters, seed)
+    sweeps = check_sweeps(sweeps)
+    p, m = _page_and_plane(page_u8, mask_u8)
+    dev = torch.device(device) if device is not None else (p.device if p.is_cuda else torch.device("cuda:0"))
+    page, hole = p.to(dev).contiguous(), m.to(dev) != 0
+    x = (page.float() / 255.0).unsqueeze(0)
+    init = _quantise(_harmonic_fill(x, (~hole).float().unsqueeze(0), sweeps))
+    out, nnf, stats = _patch_fill(page.unsqueeze(0), hole.to(torch.uint8).unsqueeze(0), init, radius, levels, iters, seed)
+    res = (out[0], nnf[0], stats[0]) if return_field else (out[0],)
+    if isinstance(page_u8, np.ndarray):
+        res = tuple(t.cpu().numpy() for t in res)
+    else:
+        res = tuple(t if t.device == page_u8.device else t.to(page_u8.device) for t in res)
+    return res if return_field else res[0]

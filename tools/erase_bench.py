@@ -165,8 +165,13 @@ def main(argv=None):
     ap.add_argument("--seed", type=float, default=None, metavar="P", help="time the seeds stage (tsii_region_seeds): regions without a pixel above P are dropped")
     ap.add_argument("--min-seeds", type=int, default=1)
     ap.add_argument("--faint", type=float, default=0.0, metavar="SHARE", help="this share of the blobs has a logit of 1 instead of 4")
-    ap.add_argument("--filler", default="net", choices=["net", "harmonic"], help="harmonic: T.HarmonicFill in the filler stage, no inpainting net is built")
-    ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic (0..16)")
+    ap.add_argument("--filler", default="net", choices=["net", "harmonic", "patch"], help="harmonic: T.HarmonicFill, patch: T.PatchFill in the filler stage; "
+                    "no inpainting net is built")
+    ap.add_argument("--sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --filler harmonic and of the first guess of --filler patch (0..16)")
+    ap.add_argument("--patch", type=int, default=7, metavar="N", help="window of --filler patch: odd, 3..9")
+    ap.add_argument("--levels", type=int, default=4, metavar="N", help="pyramid levels of --filler patch (1..6)")
+    ap.add_argument("--iters", type=int, default=4, metavar="N", help="search iterations per level of --filler patch (1..8)")
+    ap.add_argument("--fill-seed", type=int, default=0, metavar="S", help="seed of the random search of --filler patch (32 bits)")
     ap.add_argument("--blend", action="store_true", help="time the blend stage (tsii_seamless_fill) between the filler and compose")
     ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --blend (0..16)")
     args = ap.parse_args(argv)
@@ -178,7 +183,10 @@ def main(argv=None):
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     seg = getattr(T, args.seg_model)().to(dev).eval()
-    fil = T.HarmonicFill(args.sweeps) if args.filler == "harmonic" else getattr(T, args.fill_model)().to(dev).eval()
+    if args.filler == "patch":
+        fil = T.PatchFill(args.patch, args.levels, args.iters, args.fill_seed, args.sweeps)
+    else:
+        fil = T.HarmonicFill(args.sweeps) if args.filler == "harmonic" else getattr(T, args.fill_model)().to(dev).eval()
     h, w = args.size
     page = np.ascontiguousarray((manga_tile(max(h, w), np.random.default_rng(0)).transpose(1, 2, 0)[:h, :w] * 255).astype(np.uint8))
     g = gs = P.tile_grid(h, w, args.tile, args.halo)      # gs: the segmenter's grid
@@ -446,8 +454,8 @@ def main(argv=None):
 
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
-        "seg_model": args.seg_model, "fill_model": repr(fil) if args.filler == "harmonic" else args.fill_model, "filler": args.filler,
-        "sweeps": args.sweeps if args.filler == "harmonic" else None, "tiles": g.count, "selected_tiles": n_sel,
+        "seg_model": args.seg_model, "fill_model": args.fill_model if args.filler == "net" else repr(fil), "filler": args.filler,
+        "sweeps": args.sweeps if args.filler != "net" else None, "tiles": g.count, "selected_tiles": n_sel,
         "seg_long_side": args.seg_long_side, "seg_size": [hs, ws], "seg_tiles": gs.count, "host_route_resample": host_resample,
         "text_fraction": round(n_text / npx, 4), "repeats": args.repeats, "warmup": args.warmup,
         "stage_ms": {s: {"median": round(med[s], 4), "min": round(min(v), 4), "max": round(max(v), 4)} for s, v in ms.items()},
