@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 20
+#define TSII_ABI_VERSION 21
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -111,6 +111,18 @@ size_t tsii_pw_bwd_dw_ws_bytes(int64_t m, int n, int k);
 int tsii_pw_bwd_dw(const float* dy, const float* x, int64_t m, int n, int k, const float* inv, const float* keep,
                    const float* r0, int split, const float* r1, float* dw, float* dbias,
                    void* ws, size_t ws_bytes, void* stream);
+/* K3x: tsii_pw_bwd_dx and tsii_pw_bwd_dw of one layer from ONE pass over dy (n = the wide side, k <= 128 the thin one): the same
+ * dx, dw and dbias, every argument as in those two calls.  6-product split-bf16 arithmetic only; the shape must pass
+ * tsii_pw_bwd_dxdw_ok(m, n, k, 0): m % 64 == 0, n % 32 == 0, k % 32 == 0 and (k <= 64, n <= 384) or (k <= 128, n <= 192) -- the
+ * [n x k] weight-gradient accumulators stay in registers.  _ok with min_m >= 0 accepts every such shape of at least min_m rows;
+ * min_m < 0 is the library's own choice: only the measured class, k == 64 and 256 <= n <= 384 at m >= 524288 (below that the
+ * layer is matrix-bound), everything else keeps the two calls.  ws: tsii_pw_bwd_dxdw_ws_bytes(m, n, k) bytes. */
+int tsii_pw_bwd_dxdw_ok(int64_t m, int n, int k, int64_t min_m);
+int tsii_pw_bwd_dxdw_tiles_per_block(int64_t m, int n, int k);   /* 64-row tiles one block walks on this device (0: not eligible) */
+size_t tsii_pw_bwd_dxdw_ws_bytes(int64_t m, int n, int k);
+int tsii_pw_bwd_dxdw(const float* dy, const float* x, int64_t m, int n, const float* w, int k, const float* inv,
+                     const float* keep, const float* r0, int split, const float* r1, float* dx, float* dw, float* dbias,
+                     void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K2: depth-wise partial convolution (PartialConv groups=C, MobileNetV2.py:174-176) --
  *   y[n,ho,wo,c] = keep ? (sum_taps w[c,t]*x[n,hi,wi,c]*rmask[n,hi,wi]) / denom[n,ho,wo] + b[c] : 0

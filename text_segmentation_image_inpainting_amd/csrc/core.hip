@@ -100,6 +100,16 @@ __global__ __launch_bounds__(64 * RR_LANES) void reduce_rows_vec4_kernel(const f
     }
 }
 
+static int query_cus() {
+    int dev = 0, v = 0;
+    if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || v <= 0) v = 256;
+    return v;
+}
+int device_cus() {
+    static const int cus = query_cus();      // initialised once, under the language's lock
+    return cus;
+}
+
 int launch_reduce_rows(const float* ws, int rows, int64_t len, float* out, hipStream_t stream) {
     if (len >= 4096 && len % 4 == 0 && aligned16(ws) && rows >= 8) {
         hipLaunchKernelGGL(reduce_rows_vec4_kernel, dim3(stream_grid(cdiv64(len / 4, 64) * 256, 256)), dim3(64 * RR_LANES), 0, stream, ws, rows, len / 4, out);

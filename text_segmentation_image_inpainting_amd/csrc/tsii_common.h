@@ -13,6 +13,9 @@ void set_error(const char* fmt, ...);
 // hipGetLastError() after a launch -> 0 / negative code with message
 int check_launch(const char* what);
 
+// compute units of the current device (256 if the query fails); queried once, thread-safe
+int device_cus();
+
 static inline int64_t cdiv64(int64_t a, int64_t b) { return (a + b - 1) / b; }
 static inline int cdiv(int a, int b) { return (a + b - 1) / b; }
 static inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15u) == 0; }

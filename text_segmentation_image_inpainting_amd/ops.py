@@ -26,6 +26,10 @@ FUSE_BN_BWD = True
 FUSE_BN_BWD_PW = True
 # K6d: the depth-wise dX + K6c pass also takes the layer's weight gradient (tsii_dw_bwd_dxdw_bn; stride 1 / dilation 1, bias-free)
 FUSE_DW_DXDW = True
+# K3x: dX and dW of a thin 1x1 layer from one pass over the incoming gradient (tsii_pw_bwd_dxdw) where the library finds the shape
+# eligible (tsii_pw_bwd_dxdw_ok: thin side <= 64 channels here, HBM-side row counts); everything else keeps the two calls
+FUSE_PW_DXDW = True
+PW_DXDW_MIN_M = -1      # rows from which K3x is taken; -1: the library's threshold (tests lower it to reach the kernel on small maps)
 # K6e: ... and applies the backward of the BatchNorm that FOLLOWS the layer while it loads (tsii_dw_bwd_dxdw_bn2): that BatchNorm's
 # backward only reduces its K6c partial rows (tsii_bn_bwd_reduce) and hands (gradient, raw input, constants) over; stride 1
 FUSE_DW_BN2_FOLD = True
@@ -329,7 +333,18 @@ class _Pointwise(torch.autograd.Function):
                 call("tsii_bf16_pw_bwd_dw", ptr(gy), ptr(x), m, cout, k, ptr(in_scale), ptr(in_shift), ctx.in_cfg[0], ctx.in_cfg[1],
                      ptr(dw), ptr(db), ptr(ws), nbytes, st)
             return (dx, dw, db) + (None,) * 13
-        if ctx.needs_input_grad[0]:
+        want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        if (FUSE_PW_DXDW and ctx.needs_input_grad[0] and want_w and in_scale is None and ctx.bn is None
+                and _lib.lib().tsii_pw_bwd_dxdw_ok(m, cout, k, int(PW_DXDW_MIN_M)) and _al16(gy, x)):
+            # K3x.  (A K7b layer comes here too: its dX and dW are these same two products, the addend's gradient below is untouched)
+            dx, dw = torch.empty_like(x), torch.empty_like(w)
+            db = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
+            nbytes = _lib.lib().tsii_pw_bwd_dxdw_ws_bytes(m, cout, k)
+            ws = _ws(nbytes, x)
+            call("tsii_pw_bwd_dxdw", ptr(gy), ptr(x), m, cout, ptr(w), k, ptr(inv), ptr(keep), ptr(r0), ctx.split, ptr(r1),
+                 ptr(dx), ptr(dw), ptr(db), ptr(ws), nbytes, st)
+            want_w = False
+        elif ctx.needs_input_grad[0]:
             dx = torch.empty_like(x)   # gradient w.r.t. the (virtual) normalised input when in_scale is set
             wt = _ws(_lib.lib().tsii_pw_ws_bytes(cout, k), x)
             if ctx.bn is not None and FUSE_BN_BWD_PW and k % 4 == 0 and cout % 4 == 0 and load_time_act(*ctx.in_cfg):
@@ -342,7 +357,7 @@ class _Pointwise(torch.autograd.Function):
             else:
                 call("tsii_pw_bwd_dx", ptr(gy), m, cout, ptr(w), k, ptr(inv), ptr(r0), ctx.split, ptr(r1),
                      ptr(dx), ptr(wt), st)
-        if ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2]):
+        if want_w:
             dw = torch.empty_like(w)
             db = torch.empty(cout, dtype=torch.float32, device=x.device) if ctx.has_bias else None
             nbytes = _lib.lib().tsii_pw_bwd_dw_ws_bytes(m, cout, k)
