@@ -17,6 +17,10 @@ outlines the blocks, the boxes a translation would be typeset into.
 faint and small lettering, and a region (with ``--group``: a block) stays text only if the segmenter gave at least ``--min-seeds N`` (default
 1) of its pixels more than P; the others are dropped on the device before anything is inpainted.  ``examples/evaluate.py --task eraser``
 scores a P on raw / clean pairs.
+``--geometry`` gives every kept region (with ``--group``: every block) the polygon of its convex hull and its minimum-area rotated rectangle on
+the device (``cv2.convexHull`` and ``cv2.minAreaRect`` in integers) and draws both into ``<name>_boxes.png``: the hull in green, the rectangle,
+grown to cover the pixels' squares, in blue; ``--boxes`` adds the upright boxes in red.  ``--max-vertices N`` (3..1024, default 64) bounds
+the polygon that is read back, not the rectangle.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 ``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
@@ -83,6 +87,8 @@ def main(argv=None):
     ap.add_argument("--min-area", type=int, default=0, help="drop text regions of fewer pixels (after the dilation)")
     ap.add_argument("--connectivity", type=int, default=8, choices=[4, 8])
     ap.add_argument("--boxes", action="store_true", help="also write <name>_boxes.png")
+    ap.add_argument("--geometry", action="store_true", help="hull polygon and minimum-area rotated rectangle of every kept region, drawn into <name>_boxes.png")
+    ap.add_argument("--max-vertices", type=int, default=64, metavar="N", help="hull vertices read back per region with --geometry (3..1024)")
     ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
@@ -126,7 +132,8 @@ def main(argv=None):
                           tile_batch=args.tile_batch, min_area=args.min_area, connectivity=args.connectivity, regions=args.boxes,
                           seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group,
                           smooth=args.smooth, smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
-                          tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend, blend_sweeps=args.blend_sweeps)
+                          tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend, blend_sweeps=args.blend_sweeps,
+                          geometry=args.geometry, max_vertices=args.max_vertices)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -144,13 +151,23 @@ def main(argv=None):
         clean, mask = eraser(page)
         Image.fromarray(clean).save(os.path.join(out_folder, name + "_clean.png"))
         Image.fromarray(mask).save(os.path.join(out_folder, name + "_mask.png"))
-        if args.boxes:
+        if args.boxes or args.geometry:
             from PIL import ImageDraw
             boxed = Image.fromarray(page)
             draw = ImageDraw.Draw(boxed)
-            for _, _, y0, x0, y1, x1 in eraser.last_regions["table"].tolist():
-                draw.rectangle([x0, y0, x1 - 1, y1 - 1], outline=(255, 0, 0))
+            if args.boxes:
+                for _, _, y0, x0, y1, x1 in eraser.last_regions["table"].tolist():
+                    draw.rectangle([x0, y0, x1 - 1, y1 - 1], outline=(255, 0, 0))
+            if args.geometry:
+                geo = T.RegionGeometry(None, *(eraser.last_regions[k] for k in ("n_vertices", "vertices", "rect")))
+                for r in range(len(geo.n_vertices)):
+                    for points, colour in ((geo.polygon(r), (0, 160, 0)), (geo.box_points(r, pad=True), (0, 0, 255))):
+                        xy = [(float(x), float(y)) for y, x in points]
+                        draw.line(xy + xy[:1], fill=colour)
+                print("%s: %d oriented boxes, %d of them turned by more than 5 degrees" %
+                      (name, len(geo.n_vertices), sum(5.0 < abs(geo.angle(r)) < 85.0 for r in range(len(geo.n_vertices)))))
             boxed.save(os.path.join(out_folder, name + "_boxes.png"))
+        if args.boxes:
             if args.group is not None:
                 print("%s: %d text regions in %d blocks, %d kept" % (name, eraser.last_regions["components"], eraser.last_regions["found"],
                                                                      eraser.last_regions["kept"]))

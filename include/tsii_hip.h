@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 21
+#define TSII_ABI_VERSION 22
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -1077,6 +1077,41 @@ int tsii_seamless_fill(const float* x, const float* out, const float* mask, int 
 size_t tsii_patch_fill_ws_bytes(int n, int h, int w, int radius, int levels);
 int tsii_patch_fill(const uint8_t* page, const uint8_t* hole, const uint8_t* init, int n, int h, int w, int radius, int levels, int iters,
                     uint32_t seed, uint8_t* out, int32_t* nnf, int32_t* stats, void* ws, void* stream);
+
+/* ---- K22: region geometry (csrc/hull.hip, behind K12's kernels) -- the polygon of every region's convex hull and its minimum-area
+ * enclosing rectangle (cv2.convexHull and cv2.minAreaRect of the reference's demo, per table row), on the device.  All integer: one
+ * defined answer, the same bits on every run.
+ * Inputs exactly as tsii_text_regions or tsii_text_blocks leave them: labels int32 [h,w], table int32 [max_regions,6], n_regions int32 [2]
+ * ON THE DEVICE (the call does not read it on the host); all three are read only.  R = min(n_regions[1], max_regions) table rows are in
+ * use; for r < R, P_r is the set of pixels whose label is table[r][0], taken as integer points (y, x).
+ *   Vertices.  V_r is the set of vertices of the closed convex hull of P_r, STRICT: no point of V_r lies on a segment between two others
+ *     (one pixel: one vertex; collinear pixels: the two ends).  Order: V[0] is the vertex with the smallest y and among those the smallest
+ *     x; the list then runs along the top row to the right and on around the hull, clockwise on a screen whose y points down.
+ *     n_vertices, int32 [max_regions]: n_vertices[r] = |V_r|, the TRUE count, also above max_vertices.
+ *     vertices, int32 [max_regions, max_vertices, 2]: vertices[r][k] = (y, x) of V[k] for k < min(|V_r|, max_vertices).  The slots behind
+ *     that and the rows behind R are not touched.
+ *   Rectangle.  For every hull edge k, from V[k] to V[(k + 1) mod n], with the direction d = (dy, dx) = V[k+1] - V[k] and the normal
+ *     n = (-dx, dy), both written (y part, x part): the dot products are  d . V = dy * y + dx * x  and  n . V = -dx * y + dy * x.  lo_d,
+ *     hi_d, lo_n, hi_n are the extreme dot products over ALL of V_r (never the truncated list), D = dy^2 + dx^2.  The rectangle of edge k
+ *     has the area (hi_d - lo_d) (hi_n - lo_n) / D, a rational.  The winning edge has the smallest area, compared EXACTLY by
+ *     cross-multiplication in 128 bits (no floating point); ties go to the smaller k.
+ *     rect, int64 [max_regions, 8]: rect[r] = {k, dy, dx, lo_d, hi_d, lo_n, hi_n, D} of the winning edge; rows behind R are not touched.
+ *     Its corners are the points (a d + b n) / D for a in {lo_d, hi_d}, b in {lo_n, hi_n}.
+ *     One vertex (y, x): k = -1, d = (0, 1), D = 1, lo_d = hi_d = x and, n being (-1, 0), lo_n = hi_n = n . V = -y: the SIGNED dot product
+ *     of the convention above, so that the corner formula gives (y, x) back.  Two vertices: edge 0, lo_n = hi_n.
+ * How: steps 1 to 4 of K12 (row extents, strict vertex flags of both envelopes); then a wave per region orders the flagged ends into the
+ * polygon with a scan and evaluates a lane per edge.  No allocation, no host synchronisation, everything on the caller's stream; no
+ * grid-wide barrier and no waiting on another block; integer atomics only (the row extents).
+ * ws: ws_bytes >= tsii_region_geometry_ws_bytes(h, w, max_regions, max_vertices) bytes (0: arguments refused), 4-byte aligned; it depends on
+ * the size arguments only, needs nothing cleared beforehand and holds nothing a later call depends on.  rect is 8-byte aligned.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w < 1 or > 32767 (every dot product then fits int32 and every area
+ * product int64); h*w > 2^31 - 2; max_regions < 1; max_vertices outside 3..1024; a NULL pointer; a workspace that is too small; a
+ * misaligned ws or rect.
+ * Every box or count read from table or n_regions is clamped to the page and to max_regions before use: a table that does not belong to
+ * the labels gives wrong numbers (a row without pixels: n_vertices 0, rect {-1, 0, ...}), never an access outside the buffers. */
+size_t tsii_region_geometry_ws_bytes(int h, int w, int max_regions, int max_vertices);
+int tsii_region_geometry(const int* labels, const int* table, const int* n_regions, int max_regions, int h, int w, int max_vertices,
+                         int* n_vertices, int* vertices, int64_t* rect, void* ws, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }

@@ -17,6 +17,7 @@
 //   6. finish:   one pass over the plane: bytes to 0 / 1, text pixels per tile core.
 // No grid-wide barrier, no waiting on another block: each step is its own launch.  Everything read from the table or n_regions is
 // clamped before use: a table that does not belong to the labels gives wrong bytes, never an access outside the buffers.
+// K22, region geometry, stands behind the hull's kernels in this file: it shares steps 1 to 4 with them.
 #include "emu_atomics.h"
 #include "page_grid.h"
 
@@ -101,7 +102,7 @@ __global__ __launch_bounds__(HL_THREADS) void hull_offsets_kernel(const int* __r
         if (r < R) {
             roff[r] = (int)(first < npairs ? first : npairs);
             rht[r] = first + ht <= npairs ? ht : 0;          // only a table that does not belong to the labels gets here with more
-            hull_area[r] = 0;
+            if (hull_area != nullptr) hull_area[r] = 0;     // NULL: the geometry call, which has no such column
         }
     }
     if (tid == 0) {
@@ -316,6 +317,194 @@ __global__ __launch_bounds__(HL_THREADS) void hull_finish_kernel(uint8_t* __rest
     }
 }
 
+// ==== K22: region geometry (include/tsii_hip.h, "region geometry") ====================================================================
+// The hull's vertices in order and the minimum-area enclosing rectangle of every table row.  Kernels 1-4 above run unchanged (the
+// offsets kernel without a hull_area column); behind them a wave owns a region:
+//   5g. polygon: the flagged pairs become the ordered polygon -- the first row's leftmost pixel, the right chain downwards, the left
+//                chain upwards; the two ends of the first and the last row each once.  Two passes over the region's pairs: the chains'
+//                lengths (a wave sum), then a wave scan per 64 pairs gives every vertex its place.  The full list goes to the workspace
+//                (one word per vertex: y << 16 | x, both below 2^15), the first max_vertices of it to the caller;
+//   6g. rect:    a lane per edge (lane, lane + 64, ...) walks the region's vertex list -- every lane reads the same word, the list is
+//                short and comes from L2 -- for the extreme dot products along the edge and its normal; the lanes' best edges meet in a
+//                butterfly of shuffles.  Areas are the fractions A / D with A < 2^62 and D < 2^31: compared by cross-multiplication
+//                in 128 bits made of 64-bit halves, ties to the smaller edge, so every lane ends with the same winner and its owner
+//                stores the row.
+// No atomics, no LDS, no block barrier.
+constexpr int GM_WAVES = HL_THREADS / 64;        // regions per block
+constexpr int GM_MAX_SIDE = 32767;               // every dot product fits int32, every area product int64
+
+struct GeometryWs {
+    HullWs hull;
+    int* nvert;                                  // [max_regions] vertices of a region's hull
+    int* vlist;                                  // [2 * npairs] region r's vertices from 2 * roff[r] on
+};
+static inline bool geometry_args_ok(int h, int w, int max_regions, int max_vertices, int64_t* npairs) {
+    return h <= GM_MAX_SIDE && w <= GM_MAX_SIDE && max_vertices >= 3 && max_vertices <= 1024 && hull_geometry(h, w, max_regions, npairs);
+}
+static inline size_t hull_ws_bytes(int max_regions, int64_t npairs) {
+    return (sizeof(int) * (size_t)(HL_HDR + 2 * (int64_t)max_regions + 2 * npairs) + (size_t)npairs + 3) / 4 * 4;
+}
+static inline GeometryWs geometry_ws(void* ws, int max_regions, int64_t npairs) {
+    GeometryWs r;
+    r.hull = hull_ws(ws, max_regions, npairs);
+    r.nvert = reinterpret_cast<int*>(static_cast<char*>(ws) + hull_ws_bytes(max_regions, npairs));
+    r.vlist = r.nvert + max_regions;
+    return r;
+}
+
+__device__ __forceinline__ int wave_sum(int v) {
+#pragma unroll
+    for (int d = 32; d > 0; d >>= 1) v += __shfl_xor(v, d);
+    return v;
+}
+__device__ __forceinline__ int wave_inclusive_scan(int v, int lane) {
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(v, d);
+        if (lane >= d) v += t;
+    }
+    return v;
+}
+__device__ __forceinline__ long long shfl_xor_i64(long long v, int d) {
+    const unsigned lo = __shfl_xor((unsigned)((unsigned long long)v & 0xffffffffull), d), hi = __shfl_xor((unsigned)((unsigned long long)v >> 32), d);
+    return (long long)(((unsigned long long)hi << 32) | lo);
+}
+
+// ---- 5g. polygon -----------------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ void put_vertex(int* __restrict__ vl, int* __restrict__ vo, int max_vertices, int pos, int y, int x) {
+    vl[pos] = (y << 16) | x;
+    if (pos < max_vertices) {
+        vo[2 * pos] = y;
+        vo[2 * pos + 1] = x;
+    }
+}
+
+__global__ __launch_bounds__(HL_THREADS) void geometry_polygon_kernel(int h, int w, const int* __restrict__ table, const int* __restrict__ hdr,
+                                                                      const int* __restrict__ roff, const int* __restrict__ rht,
+                                                                      const int* __restrict__ ext, const uint8_t* __restrict__ vflag,
+                                                                      int max_vertices, int* __restrict__ nvert, int* __restrict__ vlist,
+                                                                      int* __restrict__ n_vertices, int* __restrict__ vertices) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * GM_WAVES + (threadIdx.x >> 6);
+    if (r >= hdr[1]) return;                     // the whole wave, here and below
+    const int n = rht[r];
+    if (n <= 0) {                                // only a table that does not belong to the labels
+        if (lane == 0) nvert[r] = n_vertices[r] = 0;
+        return;
+    }
+    const int64_t base = roff[r];                // base + n <= npairs (offsets kernel)
+    const int y0 = clampi(table[(int64_t)r * 6 + 2], 0, h);      // y0 + n <= h
+    const int* e = ext + 2 * base;
+    const uint8_t* f = vflag + base;
+    const bool one_top = clampi(e[0], 0, w - 1) == clampi(e[1], 0, w - 1);
+    // a pair's right end is listed unless it is the first row's and that row is one pixel; its left end unless it is the first row's
+    // (the start of the list) or the last row's and that row is one pixel
+    int cr = 0, cl = 0;
+    for (int i = lane; i < n; i += 64) {
+        const int fl = f[i];
+        cr += (fl & 2) && !(i == 0 && one_top);
+        cl += (fl & 1) && i > 0 && !(i == n - 1 && clampi(e[2 * i], 0, w - 1) == clampi(e[2 * i + 1], 0, w - 1));
+    }
+    const int nr = wave_sum(cr), nl = wave_sum(cl), total = 1 + nr + nl;     // <= 2 n
+    int* vl = vlist + 2 * base;
+    int* vo = vertices + (int64_t)r * max_vertices * 2;
+    if (lane == 0) {
+        put_vertex(vl, vo, max_vertices, 0, y0, clampi(e[0], 0, w - 1));
+        nvert[r] = n_vertices[r] = total;
+    }
+    int before_r = 0, before_l = 0;              // listed ends in the rows above this chunk
+    for (int i0 = 0; i0 < n; i0 += 64) {
+        const int i = i0 + lane;
+        int er = 0, el = 0, xl = 0, xr = 0;
+        if (i < n) {
+            const int fl = f[i];
+            xl = clampi(e[2 * i], 0, w - 1);
+            xr = clampi(e[2 * i + 1], 0, w - 1);
+            er = (fl & 2) && !(i == 0 && one_top);
+            el = (fl & 1) && i > 0 && !(i == n - 1 && xl == xr);
+        }
+        const int sr = wave_inclusive_scan(er, lane), sl = wave_inclusive_scan(el, lane);
+        if (er) put_vertex(vl, vo, max_vertices, before_r + sr, y0 + i, xr);                        // 1 + the ends above it
+        if (el) put_vertex(vl, vo, max_vertices, 1 + nr + nl - (before_l + sl), y0 + i, xl);      // 1 + nr + the ends below it
+        before_r += __shfl(sr, 63);
+        before_l += __shfl(sl, 63);
+    }
+}
+
+// ---- 6g. rect --------------------------------------------------------------------------------------------------------------------
+struct U128 { unsigned long long hi, lo; };
+__device__ __forceinline__ U128 mul_64x64(unsigned long long a, unsigned long long b) {
+    const unsigned long long a0 = a & 0xffffffffull, a1 = a >> 32, b0 = b & 0xffffffffull, b1 = b >> 32;
+    const unsigned long long p00 = a0 * b0, p01 = a0 * b1, p10 = a1 * b0, p11 = a1 * b1;
+    const unsigned long long mid = (p00 >> 32) + (p01 & 0xffffffffull) + (p10 & 0xffffffffull);
+    U128 r;
+    r.lo = (p00 & 0xffffffffull) | (mid << 32);
+    r.hi = p11 + (p01 >> 32) + (p10 >> 32) + (mid >> 32);
+    return r;
+}
+// the rectangle of edge k1, area a1 / d1, comes before that of k2: the smaller area, then the smaller edge; k < 0: no edge yet
+__device__ __forceinline__ bool rect_before(long long a1, int d1, int k1, long long a2, int d2, int k2) {
+    if (k1 < 0) return false;
+    if (k2 < 0) return true;
+    const U128 p = mul_64x64((unsigned long long)a1, (unsigned long long)d2), q = mul_64x64((unsigned long long)a2, (unsigned long long)d1);
+    if (p.hi != q.hi) return p.hi < q.hi;
+    if (p.lo != q.lo) return p.lo < q.lo;
+    return k1 < k2;
+}
+
+__global__ __launch_bounds__(HL_THREADS) void geometry_rect_kernel(const int* __restrict__ hdr, const int* __restrict__ roff,
+                                                                   const int* __restrict__ nvert, const int* __restrict__ vlist,
+                                                                   long long* __restrict__ rect) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * GM_WAVES + (threadIdx.x >> 6);
+    if (r >= hdr[1]) return;                     // the whole wave, here and below
+    const int n = nvert[r];
+    long long* out = rect + 8 * (int64_t)r;
+    if (n <= 0) {
+        if (lane < 8) out[lane] = lane == 0 ? -1 : 0;
+        return;
+    }
+    const int* vl = vlist + 2 * (int64_t)roff[r];
+    if (n == 1) {                                // d = (0, 1), n = (-1, 0): d . V = x, n . V = -y
+        if (lane == 0) {
+            const long long y = vl[0] >> 16, x = vl[0] & 0xffff;
+            out[0] = -1; out[1] = 0; out[2] = 1; out[3] = x; out[4] = x; out[5] = -y; out[6] = -y; out[7] = 1;
+        }
+        return;
+    }
+    int k_best = -1, dy_best = 0, dx_best = 0, d_best = 1, lo_d_best = 0, hi_d_best = 0, lo_n_best = 0, hi_n_best = 0;
+    long long a_best = 0;
+    for (int k = lane; k < n; k += 64) {
+        const int p = vl[k], q = vl[k + 1 == n ? 0 : k + 1];
+        const int dy = (q >> 16) - (p >> 16), dx = (q & 0xffff) - (p & 0xffff);
+        int lo_d = INT_MAX, hi_d = INT_MIN, lo_n = INT_MAX, hi_n = INT_MIN;
+        for (int j = 0; j < n; ++j) {
+            const int v = vl[j], y = v >> 16, x = v & 0xffff;
+            const int pd = dy * y + dx * x, pn = dy * x - dx * y;        // |.| <= 2 * 32766^2 < 2^31
+            lo_d = pd < lo_d ? pd : lo_d; hi_d = pd > hi_d ? pd : hi_d;
+            lo_n = pn < lo_n ? pn : lo_n; hi_n = pn > hi_n ? pn : hi_n;
+        }
+        const long long a = ((long long)hi_d - lo_d) * ((long long)hi_n - lo_n);
+        const int d = dy * dy + dx * dx;
+        if (rect_before(a, d, k, a_best, d_best, k_best)) {
+            k_best = k; a_best = a; d_best = d; dy_best = dy; dx_best = dx;
+            lo_d_best = lo_d; hi_d_best = hi_d; lo_n_best = lo_n; hi_n_best = hi_n;
+        }
+    }
+    int k_win = k_best, d_win = d_best;
+    long long a_win = a_best;
+#pragma unroll
+    for (int s = 32; s > 0; s >>= 1) {
+        const int k2 = __shfl_xor(k_win, s), d2 = __shfl_xor(d_win, s);
+        const long long a2 = shfl_xor_i64(a_win, s);
+        if (rect_before(a2, d2, k2, a_win, d_win, k_win)) { k_win = k2; d_win = d2; a_win = a2; }
+    }
+    if (k_best >= 0 && k_best == k_win) {        // one lane: an edge belongs to one lane
+        out[0] = k_best; out[1] = dy_best; out[2] = dx_best; out[3] = lo_d_best; out[4] = hi_d_best; out[5] = lo_n_best; out[6] = hi_n_best;
+        out[7] = d_best;
+    }
+}
+
 }  // namespace tsii
 
 using namespace tsii;
@@ -323,7 +512,7 @@ using namespace tsii;
 extern "C" size_t tsii_region_hulls_ws_bytes(int h, int w, int max_regions) {
     int64_t npairs;
     if (!hull_geometry(h, w, max_regions, &npairs)) return 0;
-    return (sizeof(int) * (size_t)(HL_HDR + 2 * (int64_t)max_regions + 2 * npairs) + (size_t)npairs + 3) / 4 * 4;
+    return hull_ws_bytes(max_regions, npairs);
 }
 
 extern "C" int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions, int max_regions,
@@ -348,4 +537,38 @@ extern "C" int tsii_region_hulls(uint8_t* text, const int* labels, int h, int w,
     hipLaunchKernelGGL(hull_fill_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, text, h, w, table, s.hdr, s.roff, s.rht, s.ext, s.vflag, hull_area);
     hipLaunchKernelGGL(hull_finish_kernel, dim3((unsigned)a.napply), dim3(HL_THREADS), 0, st, text, a.g, a.nbx, a.nby, core_count);
     return check_launch("region_hulls");
+}
+
+extern "C" size_t tsii_region_geometry_ws_bytes(int h, int w, int max_regions, int max_vertices) {
+    int64_t npairs;
+    if (!geometry_args_ok(h, w, max_regions, max_vertices, &npairs)) return 0;
+    return hull_ws_bytes(max_regions, npairs) + sizeof(int) * (size_t)(max_regions + 2 * npairs);
+}
+
+extern "C" int tsii_region_geometry(const int* labels, const int* table, const int* n_regions, int max_regions, int h, int w, int max_vertices,
+                                    int* n_vertices, int* vertices, int64_t* rect, void* ws, size_t ws_bytes, void* stream) {
+    TSII_REQUIRE(labels && table && n_regions && n_vertices && vertices && rect && ws, "region_geometry: null pointer");
+    int64_t npairs;
+    TSII_REQUIRE(geometry_args_ok(h, w, max_regions, max_vertices, &npairs),
+                 "region_geometry: page of %d x %d pixels, max_regions %d, max_vertices %d (h, w 1..32767, max_regions >= 1, max_vertices 3..1024)",
+                 h, w, max_regions, max_vertices);
+    TSII_REQUIRE(ws_bytes >= tsii_region_geometry_ws_bytes(h, w, max_regions, max_vertices), "region_geometry: workspace of %zu bytes, %zu needed",
+                 ws_bytes, tsii_region_geometry_ws_bytes(h, w, max_regions, max_vertices));
+    TSII_REQUIRE((reinterpret_cast<uintptr_t>(ws) & 3u) == 0 && (reinterpret_cast<uintptr_t>(rect) & 7u) == 0,
+                 "region_geometry: ws must be 4-byte aligned, rect 8-byte aligned");
+    hipStream_t st = (hipStream_t)stream;
+    const GeometryWs s = geometry_ws(ws, max_regions, npairs);
+    const unsigned pair_blocks = flat_grid(npairs, HL_THREADS), region_blocks = flat_grid(max_regions, GM_WAVES);
+    hipLaunchKernelGGL(hull_offsets_kernel, dim3(1), dim3(HL_THREADS), 0, st, table, n_regions, max_regions, h, npairs, s.hull.hdr, s.hull.roff,
+                       s.hull.rht, (int*)nullptr);
+    hipLaunchKernelGGL(hull_init_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, s.hull.hdr, s.hull.ext);
+    hipLaunchKernelGGL(hull_extents_kernel, dim3(flat_grid((int64_t)h * w, HL_THREADS)), dim3(HL_THREADS), 0, st, labels, h, w, table, s.hull.hdr,
+                       s.hull.roff, s.hull.rht, s.hull.ext);
+    hipLaunchKernelGGL(hull_vertices_kernel, dim3(pair_blocks), dim3(HL_THREADS), 0, st, w, s.hull.hdr, s.hull.roff, s.hull.rht, s.hull.ext,
+                       s.hull.vflag);
+    hipLaunchKernelGGL(geometry_polygon_kernel, dim3(region_blocks), dim3(HL_THREADS), 0, st, h, w, table, s.hull.hdr, s.hull.roff, s.hull.rht,
+                       s.hull.ext, s.hull.vflag, max_vertices, s.nvert, s.vlist, n_vertices, vertices);
+    hipLaunchKernelGGL(geometry_rect_kernel, dim3(region_blocks), dim3(HL_THREADS), 0, st, s.hull.hdr, s.hull.roff, s.nvert, s.vlist,
+                       reinterpret_cast<long long*>(rect));
+    return check_launch("region_geometry");
 }

@@ -49,8 +49,8 @@ from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .fill import _seamless_fill, check_sweeps
 from .masks import MaskParts
-from .regions import (ReadBack, _flat_regions, _region_hulls, _region_seeds, _smooth_regions, _text_blocks, _text_regions, _tone_regions,
-                      check_block_args, check_flat_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
+from .regions import (ReadBack, _flat_regions, _region_geometry, _region_hulls, _region_seeds, _smooth_regions, _text_blocks, _text_regions,
+                      _tone_regions, check_block_args, check_flat_args, check_geometry_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
 
 
 class TileGrid(NamedTuple):
@@ -292,8 +292,8 @@ def _eval_mode(*nets):
 # mark before it: a stage's time on the stream is the time between those two.  Three marks close no stage: "start" (nothing is enqueued
 # yet), "joined" (the read-back tensor is formed; "counts_d2h" behind it is the copy alone) and "planned" (the host has selected the
 # tiles or planned the windows and uploaded their small index tensors).
-STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "seeds", "hulls",
-               "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
+STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "seeds", "geometry",
+               "hulls", "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
                "compose_page_u8", "compose_page_windows_u8", "download")
 
 
@@ -408,6 +408,16 @@ class TextEraser:
     ``evaluate_eraser`` on raw / clean pairs: the mask's precision and recall with and without it.  Still one synchronisation.  ``None``
     (the default): none of this runs.
 
+    ``geometry=True`` (turns the regions path on as well): every table row -- with ``group`` every block -- gets the polygon of its convex hull
+    and its minimum-area enclosing rectangle, ``cv2.convexHull`` and ``cv2.minAreaRect`` in integers on the device: the oriented box a
+    translation is typeset into, and the text angle.  The stage runs on ``last_labels`` and the table behind ``min_area``, the blocks and the
+    seeds (dropped rows get no geometry) and in front of the hulls, which then fill the same polygons.  ``last_regions`` gains ``n_vertices``
+    (numpy int32, the true count per row), ``vertices`` (int32 ``[n, max_vertices, 2]``: ``(y, x)`` from the top-left vertex clockwise, up to
+    ``max_vertices`` 3..1024 of them) and ``rect`` (int64 ``[n, 8]``: ``k, dy, dx, lo_d, hi_d, lo_n, hi_n, D``, "K22" of
+    ``include/tsii_hip.h``); ``RegionGeometry(None, n_vertices, vertices, rect)`` has the helpers ``polygon``, ``box_points``, ``size`` and
+    ``angle``.  In page pixels, also behind ``seg_long_side``; sides up to 32767.  Still one synchronisation.  ``False`` (the default): none
+    of this runs.
+
     ``blend=True``: seamless (gradient-domain, Poisson) composition of what the filler paints.  An inpainting net reproduces structure well
     and absolute level badly: its patch is plausible and a shade lighter or darker than the page around it.  The filler returns the whole
     tile, so its error ``x - clamp(out, 0, 1)`` is known at the valid pixels around every hole; between the filler and compose the harmonic
@@ -429,7 +439,8 @@ class TextEraser:
     def __init__(self, segmenter, filler, mean=(0.4935, 0.4563, 0.4544), std=(0.3769, 0.3615, 0.3566), tile=512, halo=64,
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
                  max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
-                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1, blend=False, blend_sweeps=8):
+                 smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1, blend=False, blend_sweeps=8,
+                 geometry=False, max_vertices=64):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -466,8 +477,11 @@ class TextEraser:
         if blend or blend_sweeps != 8:
             check_sweeps(blend_sweeps)
         self.blend, self.blend_sweeps = bool(blend), int(blend_sweeps)
+        if geometry or max_vertices != 64:
+            check_geometry_args(max_vertices)
+        self.geometry, self.max_vertices = bool(geometry), int(max_vertices)
         self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
-                        or self.seed is not None)
+                        or self.seed is not None or self.geometry)
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -515,7 +529,8 @@ class TextEraser:
     def _layout(self, g):
         """the page's read-back tensor: what rides where in it"""
         return ReadBack(g.count, self.max_regions, self.hull, self.group is not None, self.flat is not None, self.smooth is not None,
-                        self.tone is not None, regions=self.regions, seeds=self.seed is not None)
+                        self.tone is not None, regions=self.regions, seeds=self.seed is not None,
+                        geometry=self.max_vertices if self.geometry else 0)
 
     def _route(self, name, src, text, g, labels, own, mask_u8):
         """the flat, smooth or tone stage: fill the regions it takes and take them out of the text plane in place -> the filled page (a new
@@ -589,7 +604,7 @@ class TextEraser:
     def _enqueue_regions(self, st):
         """the regions path of phase 1, in place on ``st.text``: labelling, blocks, seeds, hulls and the flat, smooth and tone stages"""
         g, text, lay = st.g, st.text, self._layout(st.g)
-        second = whole = None
+        second = whole = geometry = None
         if self.group is None:
             self.last_labels, first = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=lay.tail + lay.extra)
             if lay.seeded:                              # the seeds' room rides behind the first tensor
@@ -606,6 +621,9 @@ class TextEraser:
             _region_seeds(text, self.last_labels, self._seed_plane(st), first, room, self.max_regions, self.min_seeds, members, g)
             st.logits = None
             self._mark("seeds")
+        if self.geometry:                               # of the labelled pixels, in front of the hulls: the fill then covers the same polygons
+            geometry = _region_geometry(self.last_labels, first[lay.routes.table], first[lay.n_regions], self.max_regions, self.max_vertices)
+            self._mark("geometry")
         if self.hull:
             _region_hulls(text, self.last_labels, first, self.max_regions, g)
             self._mark("hulls")
@@ -619,7 +637,7 @@ class TextEraser:
                 st.src = self._route(name, st.src, text, g, labels, own, None if k else st.mask_u8)
                 self._mark(name)
             st.compose_mask = torch.empty_like(st.mask_u8)      # the first stage wrote the page's mask; compose's, of the reduced plane, is scratch
-        st.read_back = lay.join(first, second, whole)
+        st.read_back = lay.join(first, second, whole, geometry)
 
     def _seed_plane(self, st):
         """the seed plane on the page's grid: ``logit > logit_of(seed)``, not dilated, through the kernels that made the text plane"""
@@ -634,7 +652,7 @@ class TextEraser:
         self._mark("counts_d2h")
         read = self._layout(st.g).unpack(host)
         if self.regions:
-            named = ("table", "found", "kept", "truncated", "members", "components", "hull_area", "seeds")
+            named = ("table", "found", "kept", "truncated", "members", "components", "hull_area", "seeds", "n_vertices", "vertices", "rect")
             self.last_regions = {k: getattr(read, k) for k in named if getattr(read, k) is not None}
             self.last_regions.update(read.stages)
         return read

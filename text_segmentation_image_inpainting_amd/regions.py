@@ -29,6 +29,10 @@ planner work per block behind it.
 ``seeded_regions`` is a hysteresis threshold: the plane was cut at a low probability; a region (with ``gap``: a block) stays only where at
 least ``min_seeds`` of its pixels are set in a second plane, cut at a high one (``tsii_region_seeds``, ``csrc/seeds.hip``; "K19: seeded
 regions").  The dropped regions leave the plane, the labels and the table on the device, before the read-back.
+
+``region_geometry`` gives every region (with ``gap``: every block) the polygon of its convex hull and its minimum-area enclosing rectangle,
+``cv2.convexHull`` and ``cv2.minAreaRect`` in integers (``tsii_region_geometry``, ``csrc/hull.hip`` behind the hull's own kernels; "K22:
+region geometry"): the oriented box a translation is typeset into, and the text angle.
 """
 from typing import NamedTuple
 
@@ -133,6 +137,50 @@ class SeededRegions(NamedTuple):
     members: np.ndarray = None
 
 
+class RegionGeometry(NamedTuple):
+    """``regions``: the ``TextRegions`` of the input (with ``gap``: its ``TextBlocks``); per table row ``r``: ``n_vertices`` (numpy int32
+    ``[n]``: the vertices of the region's convex hull, the true count), ``vertices`` (int32 ``[n, max_vertices, 2]``: ``(y, x)`` of the
+    first ``max_vertices`` of them, from the top-left one clockwise on the screen; the slots behind a row's count are 0) and ``rect`` (int64
+    ``[n, 8]``: ``k, dy, dx, lo_d, hi_d, lo_n, hi_n, D`` of the minimum-area enclosing rectangle, "K22" of ``include/tsii_hip.h``: the hull
+    edge ``k`` it lies along, the edge's direction ``d = (dy, dx)``, the extreme dot products of the hull with ``d`` and with the normal ``n =
+    (-dx, dy)``, and ``D = |d|^2``).  All integers as the device left them; the helpers below are plain numpy on them."""
+    regions: object
+    n_vertices: np.ndarray
+    vertices: np.ndarray
+    rect: np.ndarray
+
+    def polygon(self, r):
+        """int32 ``[k, 2]``: the ``(y, x)`` hull vertices of row ``r`` in order, ``k = min(n_vertices[r], max_vertices)``"""
+        return self.vertices[r, :min(int(self.n_vertices[r]), self.vertices.shape[1])].copy()
+
+    def _axes(self, r, pad):
+        _, dy, dx, lo_d, hi_d, lo_n, hi_n, dd = (float(v) for v in self.rect[r])
+        grow = 0.5 * (abs(dy) + abs(dx)) if pad else 0.0        # the support of a pixel's square along d and along n, in their units
+        return dy, dx, lo_d - grow, hi_d + grow, lo_n - grow, hi_n + grow, dd
+
+    def box_points(self, r, pad=False):
+        """float64 ``[4, 2]``: the ``(y, x)`` corners of row ``r``'s rectangle, from ``rect`` alone: ``(a d + b n) / D`` for ``(a, b)`` =
+        (lo_d, lo_n), (hi_d, lo_n), (hi_d, hi_n), (lo_d, hi_n).  It encloses the pixel CENTRES; ``pad=True`` grows it so that it covers the
+        pixels' unit squares."""
+        dy, dx, lo_d, hi_d, lo_n, hi_n, dd = self._axes(r, pad)
+        d, n = np.array([dy, dx]), np.array([-dx, dy])
+        return np.stack([(a * d + b * n) / dd for a, b in ((lo_d, lo_n), (hi_d, lo_n), (hi_d, hi_n), (lo_d, hi_n))])
+
+    def size(self, r, pad=False):
+        """(along, across): the rectangle's side along its edge ``d`` and the one across it, in pixels; their product is the area"""
+        _, _, lo_d, hi_d, lo_n, hi_n, dd = self._axes(r, pad)
+        return (hi_d - lo_d) / np.sqrt(dd), (hi_n - lo_n) / np.sqrt(dd)
+
+    def angle(self, r):
+        """degrees from the x axis to the rectangle's LONGER side (the edge's direction where both are equal), in ``(-90, 90]``; positive
+        turns towards +y, clockwise on a screen whose y points down"""
+        _, dy, dx, lo_d, hi_d, lo_n, hi_n, _ = (int(v) for v in self.rect[r])
+        if hi_n - lo_n > hi_d - lo_d:
+            dy, dx = dx, -dy                                    # the normal's line
+        a = float(np.degrees(np.arctan2(dy, dx)))
+        return a - 180.0 if a > 90.0 else a + 180.0 if a <= -90.0 else a
+
+
 def _check_int_range(name, value, lo, hi):
     if isinstance(value, bool) or int(value) != value or not lo <= value <= hi:
         raise ValueError(f"{name} {value} must be an integer {lo}..{hi}")
@@ -204,6 +252,7 @@ class PageRead(NamedTuple):
     worked on), ``stages`` and ``gone`` as ``unpack_routes`` gives them: None, {} and None without such a stage.  ``plan_table`` /
     ``plan_truncated``: the regions that still hold text, for ``plan_fill_windows``.  ``seeds`` (the seed pixels of each table row),
     ``seed_dropped`` / ``seed_dropped_pixels`` (the rows ``tsii_region_seeds`` took out, their summed area): with ``seeds``, else None.
+    ``n_vertices`` / ``vertices`` / ``rect``: with ``geometry``, of each table row (``RegionGeometry``), else None.
     Without the regions path all but ``counts`` is None."""
     counts: np.ndarray
     table: np.ndarray = None
@@ -221,6 +270,9 @@ class PageRead(NamedTuple):
     seeds: np.ndarray = None
     seed_dropped: int = None
     seed_dropped_pixels: int = None
+    n_vertices: np.ndarray = None
+    vertices: np.ndarray = None
+    rect: np.ndarray = None
 
 
 class ReadBack:
@@ -231,9 +283,11 @@ class ReadBack:
     words behind its table).  The last part is there with ``group``.  ``routes`` is the ``RouteLayout`` of the tensor the route stages
     work on, the second where there is one, else the first.  Without ``regions`` the tensor is the ``nt`` core counts alone.  With ``seeds``
     its LAST ``extra`` words are ``[seeds (max_regions) | dropped, dropped pixels]`` of ``tsii_region_seeds``: room the first labelling's
-    tensor -- with ``group`` the blocks' ``whole`` -- is allocated with (``seed_room``), so that nothing in front of it moves."""
+    tensor -- with ``group`` the blocks' ``whole`` -- is allocated with (``seed_room``), so that nothing in front of it moves.  With
+    ``geometry`` (the ``max_vertices`` of the stage; 0: off) the tensor of ``_region_geometry`` (``GeometryLayout``) rides behind all of
+    that, as the last ``geometry.words`` words."""
 
-    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True, seeds=False):
+    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True, seeds=False, geometry=0):
         n = int(max_regions)
         self.routes = RouteLayout(nt, n, flat, smooth, tone)
         self.regions, self.hull, self.group = bool(regions), bool(hull), bool(group)
@@ -249,6 +303,9 @@ class ReadBack:
         self.extra = n + 2 if self.seeded else 0
         self.seed_words, self.seed_dropped = slice(self.words, self.words + n), slice(self.words + n, self.words + self.extra)
         self.words += self.extra
+        self.geometry = GeometryLayout(n, geometry) if geometry and self.regions else None
+        self.geometry_words = slice(self.words, self.words + (self.geometry.words if self.geometry else 0))
+        self.words = self.geometry_words.stop
 
     def seed_room(self, whole):
         """(members, room) on the device for ``_region_seeds``: ``whole`` is the first labelling's tensor as allocated, ``[first | members,
@@ -257,7 +314,12 @@ class ReadBack:
         assert self.seeded and whole.numel() == self.first.stop + (n + 1 if self.group else 0) + self.extra
         return (whole[self.first.stop:self.first.stop + n] if self.group else None), whole[whole.numel() - self.extra:]
 
-    def join(self, first, second=None, whole=None):
+    def join(self, first, second=None, whole=None, geometry=None):
+        """``_join`` of the stages' tensors, with the tensor of ``_region_geometry`` behind it where that stage ran"""
+        joined = self._join(first, second, whole)
+        return joined if geometry is None else torch.cat([joined, geometry])
+
+    def _join(self, first, second=None, whole=None):
         """the tensor to copy, from what the stages left on the device: ``first``, ``second`` (None where the route stages worked on
         ``first``) and, with ``group`` or ``seeds``, ``whole``: the tensor as allocated (``_text_blocks``', or ``_text_regions``' with the
         seeds' room behind it), whose front ``first`` is.  Copies only where a tensor has to
@@ -285,6 +347,8 @@ class ReadBack:
         if self.seeded:
             read = read._replace(seeds=host[self.seed_words][:n].copy(), seed_dropped=dropped,
                                  seed_dropped_pixels=int(host[self.seed_dropped][1]))
+        if self.geometry is not None:
+            read = read._replace(**dict(zip(("n_vertices", "vertices", "rect"), self.geometry.unpack(host[self.geometry_words], n))))
         return read
 
 
@@ -347,6 +411,45 @@ def _region_hulls(text, labels, packed, max_regions, grid=None):
     tile, halo = (0, 0) if grid is None else (grid.tile, grid.halo)
     call("tsii_region_hulls", ptr(text), ptr(labels), h, w, ptr(packed[nt + 2:]), ptr(packed[nt:nt + 2]), n, tile, halo,
          ptr(packed[:nt]) if nt else None, ptr(packed[nt + 2 + 6 * n:]), ptr(ws), _lib.stream())
+
+
+class GeometryLayout:
+    """The words of the ONE int32 tensor ``_region_geometry`` leaves for the read-back, ``[rect (16 per row: 8 int64) | n_vertices (1) |
+    vertices (2 * max_vertices)]``: the rectangles stand first, so that they are 8-byte aligned in a tensor of their own."""
+
+    def __init__(self, max_regions, max_vertices):
+        n, m = int(max_regions), int(max_vertices)
+        self.max_regions, self.max_vertices = n, m
+        self.rect, self.n_vertices = slice(0, 16 * n), slice(16 * n, 17 * n)
+        self.vertices = slice(17 * n, 17 * n + 2 * n * m)
+        self.words = self.vertices.stop
+
+    def unpack(self, host, rows):
+        """host copy of the tensor -> (n_vertices ``[rows]``, vertices ``[rows, max_vertices, 2]``, rect int64 ``[rows, 8]``), copies; the
+        vertex slots behind a row's count are 0, as the tensor was allocated"""
+        rect = host[self.rect].copy().view(np.int64).reshape(self.max_regions, 8)[:rows].copy()
+        vertices = host[self.vertices].reshape(self.max_regions, self.max_vertices, 2)[:rows].copy()
+        return host[self.n_vertices][:rows].copy(), vertices, rect
+
+
+def check_geometry_args(max_vertices):
+    _check_int_range("max_vertices", max_vertices, 3, 1024)
+
+
+def _region_geometry(labels, table, n_regions, max_regions, max_vertices):
+    """``tsii_region_geometry`` on the current stream, behind ``_text_regions`` or ``_text_blocks``: ``labels``, ``table`` (the device words
+    of the table) and ``n_regions`` (the device pair) as they left them, all read only -> the int32 device tensor of ``GeometryLayout``."""
+    h, w = int(labels.shape[0]), int(labels.shape[1])
+    lay = GeometryLayout(max_regions, max_vertices)
+    assert labels.dtype == torch.int32 and labels.is_contiguous() and table.dtype == torch.int32 and table.numel() >= 6 * lay.max_regions
+    nbytes = int(_lib.lib().tsii_region_geometry_ws_bytes(h, w, lay.max_regions, lay.max_vertices))
+    if nbytes == 0:
+        raise ValueError(f"region geometry: a page of {h} x {w} pixels (sides up to 32767), {max_regions} regions, {max_vertices} vertices: out of range")
+    geo = torch.zeros((lay.words,), dtype=torch.int32, device=labels.device)
+    ws = ops._ws(nbytes, labels)
+    call("tsii_region_geometry", ptr(labels), ptr(table), ptr(n_regions), lay.max_regions, h, w, lay.max_vertices, ptr(geo[lay.n_vertices]),
+         ptr(geo[lay.vertices]), ptr(geo[lay.rect]), ptr(ws), nbytes, _lib.stream())
+    return geo
 
 
 def _region_seeds(text, labels, seed, packed, room, max_regions, min_seeds, members=None, grid=None):
@@ -634,6 +737,36 @@ def seeded_regions(mask_u8, seed_u8, min_seeds=1, connectivity=8, min_area=0, ga
     r = rb.unpack(whole.cpu().numpy())
     return SeededRegions(_like(plane * 255, mask_u8), _like(labels, mask_u8), r.table, r.seeds, r.found, r.kept, r.seed_dropped,
                          r.seed_dropped_pixels, r.truncated, r.members)
+
+
+def region_geometry(mask_u8, connectivity=8, min_area=0, max_regions=4096, max_vertices=64, gap=None, device=None) -> RegionGeometry:
+    """The hull polygon and the minimum-area enclosing rectangle of every text region: ``cv2.convexHull`` and ``cv2.minAreaRect`` per region,
+    on the device and in integers.  ``mask_u8``: ``[H, W]`` uint8, numpy or torch, host or device, sides up to 32767; non-zero = text (the 255
+    masks ``TextEraser`` returns work directly); it is not modified.  Regions below ``min_area`` are dropped first, as in ``text_regions``;
+    with ``gap`` (1..64) the regions are grouped into blocks first, as in ``text_blocks``, and ``regions`` is the ``TextBlocks``.  Up to
+    ``max_vertices`` (3..1024) vertices per row come back; ``n_vertices`` is the true count and the rectangle is always that of the whole
+    hull.  Kept regions beyond ``max_regions`` get no geometry.  Labels come back the same kind and on the same device as ``mask_u8``; one
+    synchronisation (the read-back of the counts, the table, the vertices and the rectangles).  A host plane is computed on ``device``
+    (default ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_geometry_args(max_vertices)
+    if gap is not None:
+        check_block_args(gap)
+    plane = _plane_on_device(mask_u8, device)
+    rb = ReadBack(0, max_regions, group=gap is not None, geometry=max_vertices)
+    if gap is None:
+        labels, first = _text_regions(plane, connectivity, min_area, max_regions)
+        whole = None
+    else:
+        every, counts = _text_regions(plane, connectivity, 0, 0)
+        labels, first, whole = _text_blocks(plane, every, counts, gap, min_area, max_regions)
+    geo = _region_geometry(labels, first[rb.routes.table], first[rb.n_regions], max_regions, max_vertices)
+    r = rb.unpack(rb.join(first, None, whole, geo).cpu().numpy())
+    if gap is None:
+        regions = TextRegions(_like(labels, mask_u8), r.table, r.found, r.kept, r.truncated)
+    else:
+        regions = TextBlocks(_like(plane * 255, mask_u8), _like(labels, mask_u8), r.table, r.members, r.found, r.kept, r.components)
+    return RegionGeometry(regions, r.n_vertices, r.vertices, r.rect)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:
