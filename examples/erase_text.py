@@ -21,6 +21,9 @@ scores a P on raw / clean pairs.
 the device (``cv2.convexHull`` and ``cv2.minAreaRect`` in integers) and draws both into ``<name>_boxes.png``: the hull in green, the rectangle,
 grown to cover the pixels' squares, in blue; ``--boxes`` adds the upright boxes in red.  ``--max-vertices N`` (3..1024, default 64) bounds
 the polygon that is read back, not the rectangle.
+``--crops HxW`` cuts every kept region's (with ``--group``: every block's) rotated rectangle out of the raw page on the device, deskewed and
+scaled into a slot of H x W pixels, and writes the first ``--max-crops N`` (default 64) as ``<name>_crop_NN.png``: what an OCR or translation
+step reads.  ``--crop-orient long`` lays vertical columns along the slot's width instead of keeping them upright.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 ``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
@@ -89,6 +92,9 @@ def main(argv=None):
     ap.add_argument("--boxes", action="store_true", help="also write <name>_boxes.png")
     ap.add_argument("--geometry", action="store_true", help="hull polygon and minimum-area rotated rectangle of every kept region, drawn into <name>_boxes.png")
     ap.add_argument("--max-vertices", type=int, default=64, metavar="N", help="hull vertices read back per region with --geometry (3..1024)")
+    ap.add_argument("--crops", default=None, metavar="HxW", help="write every kept region's deskewed crop, fitted into H x W pixels, as <name>_crop_NN.png")
+    ap.add_argument("--crop-orient", default="upright", choices=["upright", "long"], help="long: columns are laid along the crop's width")
+    ap.add_argument("--max-crops", type=int, default=64, metavar="N", help="crops written per page with --crops")
     ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
@@ -133,7 +139,9 @@ def main(argv=None):
                           seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack, flat=args.flat, flat_ring=args.flat_ring, group=args.group,
                           smooth=args.smooth, smooth_ring=args.smooth_ring, smooth_sweeps=args.smooth_sweeps, tone=args.tone, tone_ring=args.tone_ring,
                           tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend, blend_sweeps=args.blend_sweeps,
-                          geometry=args.geometry, max_vertices=args.max_vertices)
+                          geometry=args.geometry, max_vertices=args.max_vertices,
+                          crops=None if args.crops is None else tuple(int(v) for v in args.crops.lower().split("x")), max_crops=args.max_crops,
+                          crop_orient=args.crop_orient)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -151,6 +159,12 @@ def main(argv=None):
         clean, mask = eraser(page)
         Image.fromarray(clean).save(os.path.join(out_folder, name + "_clean.png"))
         Image.fromarray(mask).save(os.path.join(out_folder, name + "_mask.png"))
+        if args.crops is not None:
+            found = eraser.last_regions["crops"]
+            for r in range(len(found.info)):
+                if found.info[r, 0]:
+                    Image.fromarray(found.crop(r).cpu().numpy()).save(os.path.join(out_folder, "%s_crop_%02d.png" % (name, r)))
+            print("%s: %d crops" % (name, len(found.info)))
         if args.boxes or args.geometry:
             from PIL import ImageDraw
             boxed = Image.fromarray(page)

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 22
+#define TSII_ABI_VERSION 23
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -1112,6 +1112,45 @@ int tsii_patch_fill(const uint8_t* page, const uint8_t* hole, const uint8_t* ini
 size_t tsii_region_geometry_ws_bytes(int h, int w, int max_regions, int max_vertices);
 int tsii_region_geometry(const int* labels, const int* table, const int* n_regions, int max_regions, int h, int w, int max_vertices,
                          int* n_vertices, int* vertices, int64_t* rect, void* ws, size_t ws_bytes, void* stream);
+
+/* ---- K23: region crops (csrc/crops.hip) -- every table row's minimum-area rectangle cut out of the raw page on the device, deskewed, scaled
+ * into a fixed slot and batched: the picture an OCR or typesetting step starts from.  All integer: one defined answer, the same bits on
+ * every run.
+ * page: uint8 [h,w,3], read only.  rect int64 [max_regions,8] and n_regions int32 [2] exactly as tsii_region_geometry leaves them, ON THE
+ * DEVICE (the call does not read them on the host), read only.  R = min(n_regions[1], max_regions, max_crops) rows are served; info rows
+ * and slots behind R are not touched.  info: int32 [max_crops,10]; crops: uint8 [max_crops,ch,cw,3].
+ *   Padded rectangle.  rect[r] = (k, dy, dx, lo_d, hi_d, lo_n, hi_n, D).  D <= 0 (a row without pixels): info[r] = 0 and the whole slot is
+ *     `fill`.  Otherwise pad = |dy| + |dx| and, in DOUBLED dot-product units, A0 = 2 lo_d - pad, A1 = 2 hi_d + pad, B0 = 2 lo_n - pad,
+ *     B1 = 2 hi_n + pad: the rectangle grown to cover the pixels' unit squares, never degenerate.
+ *   Frame.  f in 0..3 gives the crop's x axis u, its y axis v (u turned clockwise on the screen) and the ranges [U0, U1] along u and
+ *     [V0, V1] along v; d = (dy, dx) and n = (-dx, dy) are written (y part, x part) as in K22:
+ *       f = 0: u =  d, v = -n, [A0, A1], [-B1, -B0]        f = 1: u = -n, v = -d, [-B1, -B0], [-A1, -A0]
+ *       f = 2: u = -d, v =  n, [-A1, -A0], [B0, B1]        f = 3: u =  n, v =  d, [B0, B1], [A0, A1]
+ *     The x parts of u are dx, -dy, -dx, dy.  Eu = U1 - U0, Ev = V1 - V0.
+ *     orient = 0 ("upright"): the smallest f whose u has the largest x part -- deskewed by at most 45 degrees, never laid on its side.
+ *     orient = 1 ("long"): only the frames with Eu >= Ev (Eu == Ev: all four); the largest x part of u, ties to the larger y part of u,
+ *     then to the smaller f -- a column is turned so that reading downwards becomes reading rightwards.
+ *   Fit.  If Eu * ch >= Ev * cw: uw = cw, uh = clamp((2 cw Ev + Eu) / (2 Eu), 1, ch); otherwise uh = ch,
+ *     uw = clamp((2 ch Eu + Ev) / (2 Ev), 1, cw).  Small blocks are magnified, large ones reduced.
+ *   Supersampling.  s is the smallest number in 1..max_ss with (s uw)^2 D >= (Eu / 2)^2 and (s uh)^2 D >= (Ev / 2)^2, or max_ss where none
+ *     has both (Eu / 2 < 2^32: both sides fit unsigned 64 bits): about one source pixel per sub-sample at the most.
+ *   Fixed point.  All divisions are floor divisions (towards minus infinity); everything fits int64.  In units of 2^-12 pixel, per
+ *     component: O = floor((U0 u + V0 v) * 2048 / D), SU = floor(Eu u * 2048 / D), SV = floor(Ev v * 2048 / D).
+ *     info[r] = (uh, uw, f, s, O_y, O_x, SU_y, SU_x, SV_y, SV_x).
+ *   Samples.  Sub-sample (l, m), l < uh s, m < uw s: P = O + floor(SU (2m + 1) / (2 uw s)) + floor(SV (2l + 1) / (2 uh s)) per component;
+ *     iy = P_y >> 12, fy = (P_y & 4095) >> 4, the same for x; the four neighbours (iy, iy + 1) x (ix, ix + 1), each index clamped to the
+ *     page; per channel t = (256 - fy) ((256 - fx) p00 + fx p01) + fy ((256 - fx) p10 + fx p11).  Crop pixel (i, j), i < uh, j < uw, is
+ *     (the sum of t over its s x s sub-samples + 32768 s^2) / (65536 s^2).  Slot pixels outside uh x uw are `fill`.
+ *   Validation.  A row is served as a row without pixels (info 0, slot `fill`) unless 1 <= D <= 2^31, |dy| and |dx| <= 32767, lo <= hi and
+ *     |lo|, |hi| <= 2^31 - 65536 on both axes, Eu and Ev >= 1 and O, SU and SV fit int32: every row tsii_region_geometry writes for a page
+ *     of sides up to 32767 passes.  The count is clamped and every page index is clamped to the page: a foreign table gives wrong
+ *     pictures, never an access outside the buffers.
+ * No workspace, no allocation, no host synchronisation, no atomics, no floating point; everything on the caller's stream.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w outside 1..32767; max_regions < 1; max_crops < 1; ch or cw outside
+ * 1..4096; max_crops * ch * cw * 3 > 2^31 - 1; orient not 0 or 1; fill outside 0..255; max_ss outside 1..4; a NULL pointer; a misaligned
+ * rect (8 bytes) or info (4 bytes). */
+int tsii_region_crops(const uint8_t* page, int h, int w, const int64_t* rect, const int* n_regions, int max_regions, int max_crops, int ch,
+                      int cw, int orient, int fill, int max_ss, int* info, uint8_t* crops, void* stream);
 
 #ifdef __cplusplus
 }

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 22        # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 23        # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -202,6 +202,8 @@ SIGNATURES = {
     # K22 region geometry (csrc/hull.hip): int32 labels / table / counts in, int32 vertices and int64 rectangles out; ws_bytes is a size_t
     "tsii_region_geometry_ws_bytes": (_z, [_i, _i, _i, _i]),
     "tsii_region_geometry": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
+    # K23 region crops (csrc/crops.hip): uint8 page, int64 rectangles and int32 counts in, int32 info and uint8 slots out
+    "tsii_region_crops": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
 }
 
 _LIB = None

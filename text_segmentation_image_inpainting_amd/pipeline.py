@@ -49,8 +49,9 @@ from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .fill import _seamless_fill, check_sweeps
 from .masks import MaskParts
-from .regions import (ReadBack, _flat_regions, _region_geometry, _region_hulls, _region_seeds, _smooth_regions, _text_blocks, _text_regions,
-                      _tone_regions, check_block_args, check_flat_args, check_geometry_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
+from .regions import (ReadBack, RegionCrops, _flat_regions, _region_crops, _region_geometry, _region_hulls, _region_seeds, _smooth_regions,
+                      _text_blocks, _text_regions, _tone_regions, check_block_args, check_crop_args, check_flat_args, check_geometry_args,
+                      check_region_args, check_seed_args, check_smooth_args, check_tone_args)
 
 
 class TileGrid(NamedTuple):
@@ -293,7 +294,7 @@ def _eval_mode(*nets):
 # yet), "joined" (the read-back tensor is formed; "counts_d2h" behind it is the copy alone) and "planned" (the host has selected the
 # tiles or planned the windows and uploaded their small index tensors).
 STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "seeds", "geometry",
-               "hulls", "flat", "smooth", "tone", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
+               "hulls", "flat", "smooth", "tone", "crops", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
                "compose_page_u8", "compose_page_windows_u8", "download")
 
 
@@ -418,6 +419,21 @@ class TextEraser:
     ``angle``.  In page pixels, also behind ``seg_long_side``; sides up to 32767.  Still one synchronisation.  ``False`` (the default): none
     of this runs.
 
+    ``crops=(ch, cw)`` (turns ``geometry`` on, and with it the regions path): rectified crops of the lettering.  Every kept table row's
+    minimum-area rectangle -- with ``group`` every block's -- grown to cover its pixels' squares, is cut out of the RAW page on the device
+    (the text is still in it), deskewed and scaled with its aspect ratio kept into the top-left corner of a slot of ``ch x cw`` pixels
+    (sides 1..4096), the rest of the slot ``crop_fill`` (0..255): the batch an OCR net, a translation step or a review of what will be
+    erased starts from, without a per-region loop on the host.  Bilinear in integers with up to ``crop_supersample`` (1..4) squared
+    sub-samples per pixel where a block is reduced ("K23" of ``include/tsii_hip.h``): the same bits on every run.
+    ``crop_orient="upright"`` turns a block by at most 45 degrees, so a vertical column stays tall; ``"long"`` lays the longer side along
+    the slot's width, so a column reads rightwards, as a line recogniser wants it.  The stage runs behind the flat, smooth and tone stages
+    on the geometry stage's rectangles: rows that ``seed`` or ``min_area`` dropped get no crop, nor do rows beyond ``max_crops``.  The
+    slots stay on the device as ``last_crops`` (uint8 ``[max_crops, ch, cw, 3]``: ``max_crops * ch * cw * 3`` bytes, 2.4 MB at 64 slots of
+    48 x 256; slots behind the rows served hold ``crop_fill``); ``last_regions`` gains ``crops``, a ``RegionCrops`` of the first ``n =
+    min(rows, max_crops)`` slots and their ``info`` (numpy int32 ``[n, 10]``, which rides the one read-back as its last ``10 * max_crops``
+    words) with the helpers ``crop``, ``quad``, ``to_page`` and ``scale``; ``last_stats`` gains ``crops = n``.  In page pixels, also
+    behind ``seg_long_side``.  Still one synchronisation.  ``None`` (the default): none of this runs.
+
     ``blend=True``: seamless (gradient-domain, Poisson) composition of what the filler paints.  An inpainting net reproduces structure well
     and absolute level badly: its patch is plausible and a shade lighter or darker than the page around it.  The filler returns the whole
     tile, so its error ``x - clamp(out, 0, 1)`` is known at the valid pixels around every hole; between the filler and compose the harmonic
@@ -440,7 +456,7 @@ class TextEraser:
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
                  max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
                  smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1, blend=False, blend_sweeps=8,
-                 geometry=False, max_vertices=64):
+                 geometry=False, max_vertices=64, crops=None, max_crops=64, crop_orient="upright", crop_fill=255, crop_supersample=4):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -479,7 +495,11 @@ class TextEraser:
         self.blend, self.blend_sweeps = bool(blend), int(blend_sweeps)
         if geometry or max_vertices != 64:
             check_geometry_args(max_vertices)
-        self.geometry, self.max_vertices = bool(geometry), int(max_vertices)
+        if crops is not None or (max_crops, crop_orient, crop_fill, crop_supersample) != (64, "upright", 255, 4):
+            check_crop_args((1, 1) if crops is None else crops, max_crops, crop_orient, crop_fill, crop_supersample)
+        self.crops = None if crops is None else (int(crops[0]), int(crops[1]))
+        self.max_crops, self.crop_orient, self.crop_fill, self.crop_supersample = int(max_crops), crop_orient, int(crop_fill), int(crop_supersample)
+        self.geometry, self.max_vertices = bool(geometry) or self.crops is not None, int(max_vertices)
         self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
                         or self.seed is not None or self.geometry)
         self.segmenter, self.filler = segmenter, filler
@@ -496,6 +516,7 @@ class TextEraser:
         self.last_stats = None                          # of the latest page: the ``last_stats`` keys of the class docstring
         self.last_regions = None                        # its regions (regions path only): the ``last_regions`` keys of the class docstring
         self.last_labels = None                         # its int32 label plane, left on the device
+        self.last_crops = None                          # its crops (``crops`` only): uint8 ``[max_crops, ch, cw, 3]``, left on the device
         self.last_route_labels = None                   # the int32 label plane the flat, smooth and tone stages worked on, left on the device; None unless one of them is enabled
 
     # A page runs in three phases over one PageState: _enqueue, _read_back (the one synchronisation) and _finish with _download behind
@@ -530,7 +551,7 @@ class TextEraser:
         """the page's read-back tensor: what rides where in it"""
         return ReadBack(g.count, self.max_regions, self.hull, self.group is not None, self.flat is not None, self.smooth is not None,
                         self.tone is not None, regions=self.regions, seeds=self.seed is not None,
-                        geometry=self.max_vertices if self.geometry else 0)
+                        geometry=self.max_vertices if self.geometry else 0, crops=self.max_crops if self.crops is not None else 0)
 
     def _route(self, name, src, text, g, labels, own, mask_u8):
         """the flat, smooth or tone stage: fill the regions it takes and take them out of the text plane in place -> the filled page (a new
@@ -604,7 +625,7 @@ class TextEraser:
     def _enqueue_regions(self, st):
         """the regions path of phase 1, in place on ``st.text``: labelling, blocks, seeds, hulls and the flat, smooth and tone stages"""
         g, text, lay = st.g, st.text, self._layout(st.g)
-        second = whole = geometry = None
+        second = whole = geometry = info = None
         if self.group is None:
             self.last_labels, first = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=lay.tail + lay.extra)
             if lay.seeded:                              # the seeds' room rides behind the first tensor
@@ -637,7 +658,11 @@ class TextEraser:
                 st.src = self._route(name, st.src, text, g, labels, own, None if k else st.mask_u8)
                 self._mark(name)
             st.compose_mask = torch.empty_like(st.mask_u8)      # the first stage wrote the page's mask; compose's, of the reduced plane, is scratch
-        st.read_back = lay.join(first, second, whole, geometry)
+        if self.crops is not None:                      # of the RAW page: the lettering is what is wanted; on the rectangles of the geometry stage
+            self.last_crops, info = _region_crops(st.page_d, geometry[lay.geometry.rect], first[lay.n_regions], self.max_regions, self.crops,
+                                                  self.max_crops, self.crop_orient, self.crop_fill, self.crop_supersample)
+            self._mark("crops")
+        st.read_back = lay.join(first, second, whole, geometry, info)
 
     def _seed_plane(self, st):
         """the seed plane on the page's grid: ``logit > logit_of(seed)``, not dilated, through the kernels that made the text plane"""
@@ -655,6 +680,8 @@ class TextEraser:
             named = ("table", "found", "kept", "truncated", "members", "components", "hull_area", "seeds", "n_vertices", "vertices", "rect")
             self.last_regions = {k: getattr(read, k) for k in named if getattr(read, k) is not None}
             self.last_regions.update(read.stages)
+            if read.crop_info is not None:
+                self.last_regions["crops"] = RegionCrops(self.last_crops[:len(read.crop_info)], read.crop_info)
         return read
 
     def _finish(self, st, read):
@@ -701,6 +728,8 @@ class TextEraser:
             self.last_stats.update(blended=self.last_stats["selected"])
         if self.seed is not None:
             self.last_stats.update(seed_dropped=read.seed_dropped, seed_dropped_pixels=read.seed_dropped_pixels)
+        if self.crops is not None:
+            self.last_stats.update(crops=len(read.crop_info))
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)

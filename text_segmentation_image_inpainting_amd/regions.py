@@ -33,6 +33,9 @@ regions").  The dropped regions leave the plane, the labels and the table on the
 ``region_geometry`` gives every region (with ``gap``: every block) the polygon of its convex hull and its minimum-area enclosing rectangle,
 ``cv2.convexHull`` and ``cv2.minAreaRect`` in integers (``tsii_region_geometry``, ``csrc/hull.hip`` behind the hull's own kernels; "K22:
 region geometry"): the oriented box a translation is typeset into, and the text angle.
+
+``region_crops`` cuts every such rectangle out of the page, deskewed and scaled into a fixed slot, and leaves the batch on the device
+(``tsii_region_crops``, ``csrc/crops.hip``; "K23: region crops"): the picture an OCR net or a reviewer starts from.
 """
 from typing import NamedTuple
 
@@ -181,6 +184,40 @@ class RegionGeometry(NamedTuple):
         return a - 180.0 if a > 90.0 else a + 180.0 if a <= -90.0 else a
 
 
+class RegionCrops(NamedTuple):
+    """``crops``: uint8 ``[n, ch, cw, 3]``, slot ``r`` the picture of table row ``r``: the row's padded minimum-area rectangle cut out of the
+    page, deskewed and scaled to ``uh x uw`` pixels in the slot's top-left corner, the rest ``fill``.  ``info``: numpy int32 ``[n, 10]``,
+    ``(uh, uw, f, s, O_y, O_x, SU_y, SU_x, SV_y, SV_x)`` per row ("K23" of ``include/tsii_hip.h``): the frame ``f``, the supersampling
+    factor ``s``, and in units of 2^-12 page pixel the rectangle's corner ``O`` and its sides ``SU`` (the crop's x axis) and ``SV`` (its y
+    axis).  A row without pixels has ``info`` 0 and an all-``fill`` slot.  The helpers are plain numpy on ``info``."""
+    crops: object
+    info: np.ndarray
+
+    def crop(self, r):
+        """the ``[uh, uw, 3]`` view of slot ``r``"""
+        return self.crops[r, :int(self.info[r, 0]), :int(self.info[r, 1])]
+
+    def quad(self, r):
+        """float64 ``[4, 2]``: the page ``(y, x)`` of the crop's corners, top-left, top-right, bottom-right, bottom-left"""
+        o, su, sv = (self.info[r, k:k + 2].astype(np.float64) / 4096.0 for k in (4, 6, 8))
+        return np.stack([o, o + su, o + su + sv, o + sv])
+
+    def to_page(self, r, i, j):
+        """the page ``(y, x)`` of the centre of crop pixel ``(i, j)`` (fractions allowed: ``(-0.5, -0.5)`` is the top-left corner)"""
+        uh, uw = int(self.info[r, 0]), int(self.info[r, 1])
+        o, su, sv = (self.info[r, k:k + 2].astype(np.float64) / 4096.0 for k in (4, 6, 8))
+        return o + su * ((2.0 * j + 1.0) / (2.0 * uw)) + sv * ((2.0 * i + 1.0) / (2.0 * uh))
+
+    def scale(self, r):
+        """(along u, along v): page pixels per crop pixel along the crop's x and y axes; below 1 where the block was magnified"""
+        uh, uw = int(self.info[r, 0]), int(self.info[r, 1])
+        return float(np.hypot(*self.info[r, 6:8].astype(np.float64))) / 4096.0 / uw, float(np.hypot(*self.info[r, 8:10].astype(np.float64))) / 4096.0 / uh
+
+
+CROP_ORIENTS = {"upright": 0, "long": 1}
+CROP_INFO = 10                                              # int32 words of info per slot
+
+
 def _check_int_range(name, value, lo, hi):
     if isinstance(value, bool) or int(value) != value or not lo <= value <= hi:
         raise ValueError(f"{name} {value} must be an integer {lo}..{hi}")
@@ -253,6 +290,7 @@ class PageRead(NamedTuple):
     ``plan_truncated``: the regions that still hold text, for ``plan_fill_windows``.  ``seeds`` (the seed pixels of each table row),
     ``seed_dropped`` / ``seed_dropped_pixels`` (the rows ``tsii_region_seeds`` took out, their summed area): with ``seeds``, else None.
     ``n_vertices`` / ``vertices`` / ``rect``: with ``geometry``, of each table row (``RegionGeometry``), else None.
+    ``crop_info``: with ``crops``, the ``info`` of the first ``min(rows, max_crops)`` table rows (``RegionCrops``), else None.
     Without the regions path all but ``counts`` is None."""
     counts: np.ndarray
     table: np.ndarray = None
@@ -273,6 +311,7 @@ class PageRead(NamedTuple):
     n_vertices: np.ndarray = None
     vertices: np.ndarray = None
     rect: np.ndarray = None
+    crop_info: np.ndarray = None
 
 
 class ReadBack:
@@ -285,9 +324,11 @@ class ReadBack:
     its LAST ``extra`` words are ``[seeds (max_regions) | dropped, dropped pixels]`` of ``tsii_region_seeds``: room the first labelling's
     tensor -- with ``group`` the blocks' ``whole`` -- is allocated with (``seed_room``), so that nothing in front of it moves.  With
     ``geometry`` (the ``max_vertices`` of the stage; 0: off) the tensor of ``_region_geometry`` (``GeometryLayout``) rides behind all of
-    that, as the last ``geometry.words`` words."""
+    that, as the last ``geometry.words`` words.  With ``crops`` (the ``max_crops`` of the stage; 0: off) the ``info`` of ``_region_crops``
+    rides behind that again: the LAST ``10 * max_crops`` words."""
 
-    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True, seeds=False, geometry=0):
+    def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True, seeds=False, geometry=0,
+                 crops=0):
         n = int(max_regions)
         self.routes = RouteLayout(nt, n, flat, smooth, tone)
         self.regions, self.hull, self.group = bool(regions), bool(hull), bool(group)
@@ -306,6 +347,9 @@ class ReadBack:
         self.geometry = GeometryLayout(n, geometry) if geometry and self.regions else None
         self.geometry_words = slice(self.words, self.words + (self.geometry.words if self.geometry else 0))
         self.words = self.geometry_words.stop
+        self.crops = int(crops) if crops and self.geometry is not None else 0
+        self.crop_words = slice(self.words, self.words + CROP_INFO * self.crops)
+        self.words = self.crop_words.stop
 
     def seed_room(self, whole):
         """(members, room) on the device for ``_region_seeds``: ``whole`` is the first labelling's tensor as allocated, ``[first | members,
@@ -314,10 +358,11 @@ class ReadBack:
         assert self.seeded and whole.numel() == self.first.stop + (n + 1 if self.group else 0) + self.extra
         return (whole[self.first.stop:self.first.stop + n] if self.group else None), whole[whole.numel() - self.extra:]
 
-    def join(self, first, second=None, whole=None, geometry=None):
-        """``_join`` of the stages' tensors, with the tensor of ``_region_geometry`` behind it where that stage ran"""
+    def join(self, first, second=None, whole=None, geometry=None, crops=None):
+        """``_join`` of the stages' tensors, with the tensor of ``_region_geometry`` and the ``info`` of ``_region_crops`` behind it where
+        those stages ran"""
         joined = self._join(first, second, whole)
-        return joined if geometry is None else torch.cat([joined, geometry])
+        return joined if geometry is None else torch.cat([joined, geometry] if crops is None else [joined, geometry, crops])
 
     def _join(self, first, second=None, whole=None):
         """the tensor to copy, from what the stages left on the device: ``first``, ``second`` (None where the route stages worked on
@@ -349,6 +394,8 @@ class ReadBack:
                                  seed_dropped_pixels=int(host[self.seed_dropped][1]))
         if self.geometry is not None:
             read = read._replace(**dict(zip(("n_vertices", "vertices", "rect"), self.geometry.unpack(host[self.geometry_words], n))))
+        if self.crops:
+            read = read._replace(crop_info=host[self.crop_words].reshape(self.crops, CROP_INFO)[:min(n, self.crops)].copy())
         return read
 
 
@@ -450,6 +497,37 @@ def _region_geometry(labels, table, n_regions, max_regions, max_vertices):
     call("tsii_region_geometry", ptr(labels), ptr(table), ptr(n_regions), lay.max_regions, h, w, lay.max_vertices, ptr(geo[lay.n_vertices]),
          ptr(geo[lay.vertices]), ptr(geo[lay.rect]), ptr(ws), nbytes, _lib.stream())
     return geo
+
+
+def check_crop_args(size, max_crops, orient, fill, supersample):
+    try:
+        ch, cw = size
+    except (TypeError, ValueError):
+        raise ValueError(f"crops {size!r} must be a pair (height, width) of the slots") from None
+    _check_int_range("crops height", ch, 1, 4096)
+    _check_int_range("crops width", cw, 1, 4096)
+    _check_int_range("max_crops", max_crops, 1, 2 ** 31 - 1)
+    if max_crops * ch * cw * 3 > 2 ** 31 - 1:
+        raise ValueError(f"max_crops {max_crops} slots of {ch} x {cw} x 3 bytes: more than 2^31 - 1 bytes")
+    if orient not in CROP_ORIENTS:
+        raise ValueError(f"crop_orient {orient!r} must be one of {sorted(CROP_ORIENTS)}")
+    _check_int_range("crop_fill", fill, 0, 255)
+    _check_int_range("crop_supersample", supersample, 1, 4)
+
+
+def _region_crops(page, rect, n_regions, max_regions, size, max_crops, orient, fill, supersample):
+    """``tsii_region_crops`` on the current stream, behind ``_region_geometry``: ``page`` (uint8 ``[h, w, 3]``), ``rect`` (the device words
+    of the rectangles, 8-byte aligned) and ``n_regions`` (the device pair) are read only -> (crops uint8 ``[max_crops, ch, cw, 3]``, info
+    int32 ``[max_crops * 10]``) on the device; slots behind the rows served are ``fill``, their info 0."""
+    h, w = int(page.shape[0]), int(page.shape[1])
+    ch, cw = int(size[0]), int(size[1])
+    assert page.dtype == torch.uint8 and page.is_contiguous() and page.dim() == 3 and page.shape[2] == 3
+    assert rect.is_contiguous() and rect.numel() * rect.element_size() >= 64 * int(max_regions)
+    crops = torch.full((int(max_crops), ch, cw, 3), int(fill), dtype=torch.uint8, device=page.device)
+    info = torch.zeros((int(max_crops) * CROP_INFO,), dtype=torch.int32, device=page.device)
+    call("tsii_region_crops", ptr(page), h, w, ptr(rect), ptr(n_regions), int(max_regions), int(max_crops), ch, cw, CROP_ORIENTS[orient], int(fill),
+         int(supersample), ptr(info), ptr(crops), _lib.stream())
+    return crops, info
 
 
 def _region_seeds(text, labels, seed, packed, room, max_regions, min_seeds, members=None, grid=None):
@@ -767,6 +845,33 @@ def region_geometry(mask_u8, connectivity=8, min_area=0, max_regions=4096, max_v
     else:
         regions = TextBlocks(_like(plane * 255, mask_u8), _like(labels, mask_u8), r.table, r.members, r.found, r.kept, r.components)
     return RegionGeometry(regions, r.n_vertices, r.vertices, r.rect)
+
+
+def region_crops(page_u8, rect, size, n_rows=None, orient="upright", fill=255, supersample=4, device=None) -> RegionCrops:
+    """Rectified crops of a page's text regions: every row of ``rect`` -- the ``rect`` of a ``RegionGeometry``, int64 ``[n, 8]``, numpy or
+    torch -- is cut out of ``page_u8`` (``[H, W, 3]`` uint8, numpy or torch, host or device, sides up to 32767; not modified) along its
+    padded minimum-area rectangle, deskewed and scaled to fit a slot of ``size = (ch, cw)`` pixels (sides 1..4096) with its aspect ratio
+    kept: bilinear, up to ``supersample`` (1..4) squared sub-samples per pixel where the block is reduced, all in integers.
+    ``orient="upright"`` turns a block by at most 45 degrees, so a column stays tall; ``"long"`` lays the longer side along the slot's
+    width, so a column reads rightwards.  The first ``n_rows`` rows (default: all) are served.  ``crops`` comes back the same kind and on
+    the same device as the page, ``n_rows * ch * cw * 3`` bytes; one synchronisation (the read-back of ``info``).  A host page is worked
+    on on ``device`` (default ``cuda:0``)."""
+    rows = np.asarray(rect.cpu() if isinstance(rect, torch.Tensor) else rect)
+    if rows.ndim != 2 or rows.shape[1] != 8 or rows.dtype != np.int64:
+        raise ValueError(f"rect must be [n, 8] int64, got {rows.shape} {rows.dtype}")
+    n = len(rows) if n_rows is None else n_rows
+    _check_int_range("n_rows", n, 0, len(rows))
+    check_crop_args(size, max(n, 1), orient, fill, supersample)
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if p.dim() != 3 or p.dtype != torch.uint8 or p.shape[2] != 3 or not 1 <= p.shape[0] <= 32767 or not 1 <= p.shape[1] <= 32767:
+        raise ValueError(f"page must be [H, W, 3] uint8 with sides 1..32767, got {tuple(p.shape)} {p.dtype}")
+    dev = torch.device(device) if device is not None else (p.device if p.is_cuda else torch.device("cuda:0"))
+    if n == 0:
+        return RegionCrops(_like(torch.zeros((0, int(size[0]), int(size[1]), 3), dtype=torch.uint8, device=dev), page_u8), np.zeros((0, CROP_INFO), np.int32))
+    rect_d = torch.from_numpy(np.ascontiguousarray(rows)).to(dev)
+    count = torch.tensor([n, n], dtype=torch.int32, device=dev)
+    crops, info = _region_crops(p.to(dev).contiguous(), rect_d, count, len(rows), size, n, orient, fill, supersample)
+    return RegionCrops(_like(crops, page_u8), info.cpu().numpy().reshape(n, CROP_INFO))
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

@@ -5,6 +5,7 @@
                                 [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
                                 [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T] [--tones SHARE] [--tone T [--tone-ring N] [--tone-period N]]
                                 [--blend [--blend-sweeps N]] [--geometry [--max-vertices N]]
+                                [--crops HxW [--crop-orient long] [--max-crops N]]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
 tsii_compose_page_u8, download.  The tool has no copy of the page's course: it puts a recorder in the place of ``TextEraser._mark``
@@ -63,6 +64,10 @@ with ``--seg-long-side`` -- then tsii_region_seeds, behind the regions / blocks 
 the regions / blocks / seeds stages) with its own pair of events; ``regions`` then reports ``hull_vertices`` and ``most_vertices``.  The stage
 grows the read-back, so ``geometry_ab`` runs the whole page with and without it, alternating, in the same process: ``page_ms`` and the
 ``d2h_int32_words`` of both.
+``--crops HxW`` (turns the geometry stage on) adds the ``crops`` stage (tsii_region_crops: every kept row's rectangle cut out of the raw page
+into a slot of H x W pixels, behind the flat / smooth / tone stages) with its own pair of events; ``regions`` then reports ``crops`` (rows
+served), ``crop_pixels`` (their pixels) and ``crop_subsamples`` (the bilinear samples behind them).  ``crops_ab`` runs the whole page with
+and without it, alternating, in the same process, as ``geometry_ab`` does.
 
 ``--blend`` adds the ``blend`` stage (tsii_seamless_fill on the filler's tiles or windows, between the filler and compose) with its own pair
 of events.  Compare with the same line without ``--blend`` in the same session, and with ``--filler harmonic``, whose filler stage is the
@@ -155,6 +160,9 @@ def main(argv=None):
     ap.add_argument("--hull", action="store_true", help="time the hulls stage (tsii_region_hulls) behind the regions stage")
     ap.add_argument("--geometry", action="store_true", help="time the geometry stage (tsii_region_geometry) behind the regions / blocks / seeds stages")
     ap.add_argument("--max-vertices", type=int, default=64, metavar="N", help="hull vertices read back per region with --geometry (3..1024)")
+    ap.add_argument("--crops", default=None, metavar="HxW", help="time the crops stage (tsii_region_crops) into slots of H x W pixels; turns --geometry on")
+    ap.add_argument("--crop-orient", default="upright", choices=["upright", "long"])
+    ap.add_argument("--max-crops", type=int, default=64, metavar="N", help="slots with --crops")
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
     ap.add_argument("--pack", action="store_true", help="windows on the text regions instead of the grid's tiles (turns the regions stage on)")
@@ -219,15 +227,18 @@ def main(argv=None):
     with_tone = args.tone is not None
     with_routes = with_flat or with_smooth or with_tone
     with_seeds = args.seed is not None
+    crop_size = None if args.crops is None else tuple(int(v) for v in args.crops.lower().split("x"))
+    args.geometry = args.geometry or crop_size is not None
     with_regions = args.min_area > 0 or args.hull or args.pack or with_blocks or with_routes or with_seeds or args.geometry
 
-    def make(select, geometry=args.geometry):
+    def make(select, geometry=args.geometry, crops=crop_size):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
                           flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth, tone=args.tone,
                           tone_ring=args.tone_ring, tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend,
-                          blend_sweeps=args.blend_sweeps, geometry=geometry, max_vertices=args.max_vertices)
+                          blend_sweeps=args.blend_sweeps, geometry=geometry, max_vertices=args.max_vertices, crops=crops,
+                          max_crops=args.max_crops, crop_orient=args.crop_orient)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -274,6 +285,9 @@ def main(argv=None):
                 region_info.update(seed_dropped=read.seed_dropped, seed_dropped_pixels=read.seed_dropped_pixels)
             if args.geometry:
                 region_info.update(hull_vertices=int(read.n_vertices.sum(dtype=np.int64)), most_vertices=int(read.n_vertices.max()) if len(read.n_vertices) else 0)
+            if crop_size is not None:
+                ci = read.crop_info.astype(np.int64)
+                region_info.update(crops=len(ci), crop_pixels=int((ci[:, 0] * ci[:, 1]).sum()), crop_subsamples=int((ci[:, 0] * ci[:, 1] * ci[:, 3] ** 2).sum()))
             if args.hull:
                 region_info["hull_pixels"] = int(read.hull_area.sum(dtype=np.int64))
             if with_routes:
@@ -320,6 +334,8 @@ def main(argv=None):
         bytes_["seeds"] = 15 * npx + (nsp + npx if with_seg else 0)     # filter 4 + 1 (+ stores where a region goes)
     if args.geometry:                       # DESIGN.md, "region geometry": extents 4 (labels); the pairs, the vertex lists and the outputs are small beside it
         bytes_["geometry"] = 4 * npx
+    if crop_size is not None:               # DESIGN.md, "region crops": 12 page bytes per sub-sample (cached: neighbours share them), 3 out per slot pixel
+        bytes_["crops"] = 12 * runs[0][5]["crop_subsamples"] + 3 * runs[0][5]["crops"] * crop_size[0] * crop_size[1]
     if args.hull:
         bytes_["hulls"] = 5 * npx + n_text  # extents 4 (labels), finish 1, the fill's stores at most once per final text pixel ("region hulls")
     if with_flat:                           # DESIGN.md, "flat regions": ring 1 (text) + apron, apply 3 + 1 in, 3 + 1 + 1 out, labels on the text
@@ -464,7 +480,7 @@ def main(argv=None):
 
     geometry_ab = None
     if args.geometry:                                       # the same page with and without the stage, alternating, in this very process
-        pair = {"with": make(True, True), "without": make(True, False)}
+        pair = {"with": make(True, True, None), "without": make(True, False, None)}
         vals, words = {k: [] for k in pair}, {}
         for i in range(args.warmup + args.repeats):
             for k, er in pair.items():
@@ -479,6 +495,24 @@ def main(argv=None):
                 words[k] = int(er._enqueue(page).read_back.numel())
         geometry_ab = {"page_ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in vals.items()},
                        "d2h_int32_words": words, "max_vertices": args.max_vertices}
+
+    crops_ab = None
+    if crop_size is not None:                               # the same page with and without the stage, alternating, in this very process
+        pair = {"with": make(True), "without": make(True, crops=None)}
+        vals, words = {k: [] for k in pair}, {}
+        for i in range(args.warmup + args.repeats):
+            for k, er in pair.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                er(page)
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    vals[k].append((time.perf_counter() - t0) * 1e3)
+        for k, er in pair.items():
+            with torch.no_grad():
+                words[k] = int(er._enqueue(page).read_back.numel())
+        crops_ab = {"page_ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in vals.items()},
+                    "d2h_int32_words": words, "slots": [args.max_crops, *crop_size], "orient": args.crop_orient}
 
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
@@ -500,7 +534,7 @@ def main(argv=None):
         "tones": args.tones, "tone": args.tone, "tone_ring": args.tone_ring if with_tone else None,
         "tone_period": args.tone_period if with_tone else None,
         "blend": args.blend, "blend_sweeps": args.blend_sweeps if args.blend else None, "blend_split_ms": blend_split,
-        "geometry": args.geometry, "geometry_ab": geometry_ab,
+        "geometry": args.geometry, "geometry_ab": geometry_ab, "crops": args.crops, "crops_ab": crops_ab,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
