@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 23
+#define TSII_ABI_VERSION 24
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -213,6 +213,20 @@ int tsii_stem_s2d(const float* x, const float* mfull, const float* r0, int split
                   int n, int h, int w, int c, int pad, float* out, void* stream);
 int tsii_stem_w_fwd(const float* w, int cout, int cin, int k, float* w2, void* stream);
 int tsii_stem_w_bwd(const float* dw2, int cout, int cin, int k, float* dw, void* stream);
+/* K4s: the stem's backward in one pass over its output gradient gy [m = n ho wo, 64]: dwk [64][12][4][4] (what tsii_dense_bwd_dw
+ * leaves for tsii_stem_w_bwd) and db [64] (may be NULL) of the 4x4 valid convolution over x2 [n, h2, w2, 12].  With y (the stem's
+ * pre-activation output, [m, 64]) the gradient of the LeakyReLU behind the stem is formed on load: dy = gy * (y > 0 ? 1 : slope),
+ * tsii_act_bwd's own product; y NULL: dy = gy.  dwk = sum dy * inv * x2 (inv NULL = ones), db = sum dy * keep (keep NULL = ones).
+ * 6-product split-bf16 arithmetic only.  tsii_stem_bwd_ok() != 0: c4 == 12, 4x4 taps, stride 1, cout == 64, wo % 64 == 0,
+ * h2 == ho + 3, w2 == wo + 3, arithmetic mode 6, gy / y / x2 16-byte aligned; everything else keeps tsii_act_bwd +
+ * tsii_dense_bwd_dw, and the entry point refuses it.  ws: tsii_stem_bwd_ws_bytes(n, ho, wo) bytes, 16-byte aligned. */
+int tsii_stem_bwd_ok(const float* gy, const float* y, const float* x2, int n, int h2, int w2, int c4, int cout,
+                     int kh, int kw, int stride, int ho, int wo);
+int tsii_stem_bwd_tiles_per_block(int n, int ho, int wo);        /* 64-pixel tiles one block walks on this device (0: not eligible) */
+size_t tsii_stem_bwd_ws_bytes(int n, int ho, int wo);
+int tsii_stem_bwd(const float* gy, const float* y, float slope, const float* inv, const float* keep, const float* x2,
+                  int n, int h2, int w2, int c4, int cout, int kh, int kw, int stride, int ho, int wo,
+                  float* dwk, float* db, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K6: BatchNorm2d (+activation, +residual)  (partial_convolution.py:193-197,
  *          residual add MobileNetV2.py:186-187, image_inpainting.py:216) ------------------

@@ -352,9 +352,11 @@ def run_nhwc(layer, x, mp):
     if hasattr(layer, "forward_nhwc"):
         return layer.forward_nhwc(x, mp)
     if isinstance(layer, nn.Sequential):
-        from .partial_convolution import PartialActivatedBN, PartialConv, PartialConv1x1, run_block
+        from .partial_convolution import PartialActivatedBN, PartialConv, PartialConv1x1, run_block, stem_act_block
         if len(layer) == 2 and isinstance(layer[0], (PartialConv, PartialConv1x1)) and isinstance(layer[1], PartialActivatedBN):
             return run_block(layer, x, mp)      # conv + BatchNorm: statistics fused into the conv (K6b)
+        if stem_act_block(layer, x):            # the stem and its LeakyReLU as one autograd node (K4s)
+            return layer[0].forward_nhwc(x, mp, act_after=act_code(layer[1].act_fn))
         for m in layer:
             x, mp = run_nhwc(m, x, mp)
         return x, mp

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 23        # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 24       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -56,6 +56,10 @@ SIGNATURES = {
     "tsii_stem_s2d": (_i, [_p, _p, _p, _i, _p, _i, _i, _i, _i, _i, _p, _p]),
     "tsii_stem_w_fwd": (_i, [_p, _i, _i, _i, _p, _p]),
     "tsii_stem_w_bwd": (_i, [_p, _i, _i, _i, _p, _p]),
+    "tsii_stem_bwd_ok": (_i, [_p, _p, _p] + [_i] * 10),
+    "tsii_stem_bwd_tiles_per_block": (_i, [_i, _i, _i]),
+    "tsii_stem_bwd_ws_bytes": (_z, [_i, _i, _i]),
+    "tsii_stem_bwd": (_i, [_p, _p, _f, _p, _p, _p] + [_i] * 10 + [_p, _p, _p, _z, _p]),
     "tsii_bn_ws_bytes": (_z, [_l, _i]),
     "tsii_bn_stats": (_i, [_p, _l, _i, _p, _p, _p, _p, _f, _p, _z, _p]),
     "tsii_bn_act_fwd": (_i, [_p, _l, _i, _p, _p, _p, _p, _f, _i, _f, _p, _p, _p]),

@@ -600,7 +600,10 @@ int launch_conv_gemm_dw(const float* dy, const float* inv, const float* x, const
     dim3 grid(cdiv(K, pl.bn), cdiv(g.cout, pl.bm), pl.splits);
     const bool elem = (mfull != nullptr || g.cin % 4 != 0);
     // 64x64 split tiles lose to the f32 kernel on the narrow stem shapes (2M x 64 x 192: 1.43 vs 1.27 ms measured): the
-    // gather form of the split kernel takes the 128x128 cases, and everything in the plain-bf16 mode
+    // gather form of the split kernel takes the 128x128 cases, and everything in the plain-bf16 mode.  The 7x7 stem of the
+    // headline workload no longer comes here in the 6-product mode: tsii_stem_bwd (stem_bwd.hip) takes it in one pass with a
+    // window loader instead of a per-element gather; what still arrives on this f32 path are the 5x5 / 3x3 stems, other
+    // channel counts, output widths that are no multiple of 64, and every stem in the other arithmetic modes
     if (!elem && (pl.big || gemm_products() == 1) && tn_split_conv_ok(dy, g.cout, x, M, g.cout, K, cg)) {
         int rc = launch_tn_split_conv(dy, g.cout, inv, x, cg, ws, M, g.cout, K, pl.chunk, pl.splits, pl.big, st);
         if (rc) return rc;

@@ -45,6 +45,10 @@ USE_HEAD_MFMA = True
 FUSE_HEAD_DLOW = True
 # K4b (stems as a space-to-depth stride-1 conv on the vector-gather GEMM)
 USE_STEM_S2D = True
+# K4s: the 7x7 stem's backward in one pass (tsii_stem_bwd): weight gradient, bias gradient and -- where the stem is followed by a plain
+# LeakyReLU (no BatchNorm) -- that activation's gradient formed on load, where the library finds the layer eligible
+# (tsii_stem_bwd_ok); everything else keeps tsii_act_bwd + tsii_dense_bwd_dw
+FUSE_STEM_BWD = True
 
 
 class Geom(NamedTuple):
@@ -656,40 +660,77 @@ class _Dense(torch.autograd.Function):
         return dx, dw, db, None, None, None, None, None, None, None, None, None
 
 
+def _stem_forward(ctx, x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, want_stats):
+    """forward of the _StemS2D family: (y, BatchNorm partials or None, x2); leaves the geometry in ctx.cfg"""
+    _lib.check_device(x)
+    x, w = x.contiguous(), w.contiguous()
+    n, h, wd, cin = x.shape
+    cout, k, pad = w.shape[0], g.kh, g.ph
+    ka, c4 = (k + 1) // 2, 4 * cin
+    h2, w2 = (h + 2 * pad) // 2, (wd + 2 * pad) // 2
+    ho, wo = g.out_hw(h, wd)
+    st, L = _lib.stream(), _lib.lib()
+    x2 = torch.empty((n, h2, w2, c4), dtype=torch.float32, device=x.device)
+    call("tsii_stem_s2d", ptr(x), ptr(mfull), ptr(r0), int(split), ptr(r1), n, h, wd, cin, pad, ptr(x2), st)
+    wk = torch.empty((cout, c4, ka, ka), dtype=torch.float32, device=x.device)
+    call("tsii_stem_w_fwd", ptr(w), cout, cin, k, ptr(wk), st)
+    g2 = Geom(ka, ka, 1, 1, 0, 0, 1, 1)
+    assert g2.out_hw(h2, w2) == (ho, wo)
+    y = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
+    nbytes = L.tsii_dense_ws_bytes(c4, cout, ka, ka)
+    ws = _ws(nbytes, x)
+    rows = int(L.tsii_dense_stat_rows(0, n, h2, w2, c4, cout, *g2, ho, wo)) if want_stats else 0
+    part = None
+    if rows > 0:
+        part = torch.empty((rows, 4, cout), dtype=torch.float32, device=x.device)
+        call("tsii_dense_fwd_bn", ptr(x2), None, None, 0, None, ptr(wk), ptr(bias), ptr(denom), ptr(keep),
+             n, h2, w2, c4, cout, *g2, ho, wo, ptr(part), ptr(y), ptr(ws), nbytes, st)
+    else:
+        call("tsii_dense_fwd", ptr(x2), None, None, 0, None, ptr(wk), ptr(bias), ptr(denom), ptr(keep),
+             n, h2, w2, c4, cout, *g2, ho, wo, ptr(y), ptr(ws), nbytes, st)
+    ctx.cfg = (tuple(w.shape), g2, (n, h2, w2, c4, ho, wo), bias is not None)
+    return y, part, x2
+
+
+def _stem_backward(ctx, x2, inv, keep, gy, y=None, slope=0.0):
+    """(dw, db) of the _StemS2D family from the gradient gy of its output; with ``y``, the stem's pre-activation output, gy is the
+    gradient BEHIND the LeakyReLU(slope) that follows the stem.  K4s (tsii_stem_bwd) takes both in one pass where it is eligible."""
+    wshape, g2, (n, h2, w2, c4, ho, wo), has_bias = ctx.cfg
+    cout, cin, k = wshape[0], wshape[1], wshape[2]
+    if not (ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2])):
+        return None, None
+    gy = gy.contiguous()
+    L, st = _lib.lib(), _lib.stream()
+    ka = g2.kh
+    dwk = torch.empty((cout, c4, ka, ka), dtype=torch.float32, device=gy.device)
+    db = torch.empty(cout, dtype=torch.float32, device=gy.device) if has_bias else None
+    if FUSE_STEM_BWD and L.tsii_stem_bwd_ok(ptr(gy), ptr(y), ptr(x2), n, h2, w2, c4, cout, ka, ka, 1, ho, wo):
+        nbytes = L.tsii_stem_bwd_ws_bytes(n, ho, wo)
+        ws = _ws(nbytes, gy)
+        call("tsii_stem_bwd", ptr(gy), ptr(y), float(slope), ptr(inv), ptr(keep), ptr(x2), n, h2, w2, c4, cout, ka, ka, 1, ho, wo,
+             ptr(dwk), ptr(db), ptr(ws), nbytes, st)
+    else:
+        if y is not None:
+            dy = torch.empty_like(gy)
+            call("tsii_act_bwd", ptr(gy), ptr(y), gy.numel(), ACT_LEAKY, float(slope), ptr(dy), st)
+            gy = dy
+        nbytes = L.tsii_dense_bwd_dw_ws_bytes(n, ho, wo, c4, cout, ka, ka)
+        ws = _ws(nbytes, gy)
+        call("tsii_dense_bwd_dw", ptr(gy), ptr(inv), ptr(keep), ptr(x2), None, None, 0, None,
+             n, h2, w2, c4, cout, *g2, ho, wo, ptr(dwk), ptr(db), ptr(ws), nbytes, st)
+    dw = torch.empty(wshape, dtype=torch.float32, device=gy.device)
+    call("tsii_stem_w_bwd", ptr(dwk), cout, cin, k, ptr(dw), st)
+    return dw, db
+
+
 class _StemS2D(torch.autograd.Function):
     """K4b: odd k, stride 2, pad (k-1)/2 conv over <= 4 input channels as a stride-1 valid conv over the space-to-depth
     image (x*mask folded into the rearrangement), on the vector-gather implicit GEMM.  No input gradient (data layer)."""
 
     @staticmethod
     def forward(ctx, x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, want_stats):
-        _lib.check_device(x)
-        x, w = x.contiguous(), w.contiguous()
-        n, h, wd, cin = x.shape
-        cout, k, pad = w.shape[0], g.kh, g.ph
-        ka, c4 = (k + 1) // 2, 4 * cin
-        h2, w2 = (h + 2 * pad) // 2, (wd + 2 * pad) // 2
-        ho, wo = g.out_hw(h, wd)
-        st, L = _lib.stream(), _lib.lib()
-        x2 = torch.empty((n, h2, w2, c4), dtype=torch.float32, device=x.device)
-        call("tsii_stem_s2d", ptr(x), ptr(mfull), ptr(r0), int(split), ptr(r1), n, h, wd, cin, pad, ptr(x2), st)
-        wk = torch.empty((cout, c4, ka, ka), dtype=torch.float32, device=x.device)
-        call("tsii_stem_w_fwd", ptr(w), cout, cin, k, ptr(wk), st)
-        g2 = Geom(ka, ka, 1, 1, 0, 0, 1, 1)
-        assert g2.out_hw(h2, w2) == (ho, wo)
-        y = torch.empty((n, ho, wo, cout), dtype=torch.float32, device=x.device)
-        nbytes = L.tsii_dense_ws_bytes(c4, cout, ka, ka)
-        ws = _ws(nbytes, x)
-        rows = int(L.tsii_dense_stat_rows(0, n, h2, w2, c4, cout, *g2, ho, wo)) if want_stats else 0
-        part = None
-        if rows > 0:
-            part = torch.empty((rows, 4, cout), dtype=torch.float32, device=x.device)
-            call("tsii_dense_fwd_bn", ptr(x2), None, None, 0, None, ptr(wk), ptr(bias), ptr(denom), ptr(keep),
-                 n, h2, w2, c4, cout, *g2, ho, wo, ptr(part), ptr(y), ptr(ws), nbytes, st)
-        else:
-            call("tsii_dense_fwd", ptr(x2), None, None, 0, None, ptr(wk), ptr(bias), ptr(denom), ptr(keep),
-                 n, h2, w2, c4, cout, *g2, ho, wo, ptr(y), ptr(ws), nbytes, st)
+        y, part, x2 = _stem_forward(ctx, x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, want_stats)
         ctx.save_for_backward(x2, inv, keep)
-        ctx.cfg = (tuple(w.shape), g2, (n, h2, w2, c4, ho, wo), bias is not None)
         ctx.set_materialize_grads(False)
         if part is not None:
             ctx.mark_non_differentiable(part)
@@ -701,21 +742,30 @@ class _StemS2D(torch.autograd.Function):
         if gy is None:
             return (None,) * 12
         x2, inv, keep = ctx.saved_tensors
-        wshape, g2, (n, h2, w2, c4, ho, wo), has_bias = ctx.cfg
-        cout, cin, k = wshape[0], wshape[1], wshape[2]
-        gy = gy.contiguous()
-        L, st = _lib.lib(), _lib.stream()
-        dw = db = None
-        if ctx.needs_input_grad[1] or (has_bias and ctx.needs_input_grad[2]):
-            ka = g2.kh
-            dwk = torch.empty((cout, c4, ka, ka), dtype=torch.float32, device=gy.device)
-            db = torch.empty(cout, dtype=torch.float32, device=gy.device) if has_bias else None
-            nbytes = L.tsii_dense_bwd_dw_ws_bytes(n, ho, wo, c4, cout, ka, ka)
-            ws = _ws(nbytes, gy)
-            call("tsii_dense_bwd_dw", ptr(gy), ptr(inv), ptr(keep), ptr(x2), None, None, 0, None,
-                 n, h2, w2, c4, cout, *g2, ho, wo, ptr(dwk), ptr(db), ptr(ws), nbytes, st)
-            dw = torch.empty(wshape, dtype=torch.float32, device=gy.device)
-            call("tsii_stem_w_bwd", ptr(dwk), cout, cin, k, ptr(dw), st)
+        dw, db = _stem_backward(ctx, x2, inv, keep, gy)
+        return (None, dw, db) + (None,) * 9
+
+
+class _StemS2DAct(torch.autograd.Function):
+    """K4s: _StemS2D followed by a plain LeakyReLU (no BatchNorm in between) as ONE node: the forward issues the same two calls
+    (the stem convolution, then tsii_act_fwd), the backward one tsii_stem_bwd that forms the activation's gradient on load."""
+
+    @staticmethod
+    def forward(ctx, x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, slope):
+        y, _, x2 = _stem_forward(ctx, x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, False)
+        out = torch.empty_like(y)
+        call("tsii_act_fwd", ptr(y), y.numel(), ACT_LEAKY, float(slope), ptr(out), _lib.stream())
+        ctx.save_for_backward(x2, inv, keep, y)
+        ctx.slope = float(slope)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return (None,) * 12
+        x2, inv, keep, y = ctx.saved_tensors
+        dw, db = _stem_backward(ctx, x2, inv, keep, gout, y, ctx.slope)
         return (None, dw, db) + (None,) * 9
 
 
@@ -916,8 +966,18 @@ def _bf16_stem_form(x, w, g: Geom):
             (x.shape[1] + 2 * g.ph) % 2 == 0 and (x.shape[2] + 2 * g.pw) % 2 == 0)
 
 
-def pconv_dense(x, w, bias, mfull, r0, split, r1, denom, keep, inv, g: Geom, want_stats=False):
-    """With ``want_stats`` returns (y, stat_part or None) -- None when the geometry is not on the implicit-GEMM path."""
+def _stem_bwd_form(x, w, g: Geom):
+    """The layers K4s is built for (tsii_stem_bwd_ok without the pointers): fp32 storage, a 7x7 _StemS2D stem over 3 channels with
+    64 output channels, an output width that is a multiple of 64, the 6-product arithmetic -- and the switch on."""
+    if not (FUSE_STEM_BWD and _ACT_STORAGE != BF16 and isinstance(x, torch.Tensor) and x.dtype == torch.float32 and _stem_form(x, w, g)):
+        return False
+    wo = g.out_hw(x.shape[1], x.shape[2])[1]
+    return (x.shape[-1] == 3 and g.kh == 7 and w.shape[0] == 64 and wo % 64 == 0 and int(_lib.lib().tsii_get_gemm_products()) == 6)
+
+
+def pconv_dense(x, w, bias, mfull, r0, split, r1, denom, keep, inv, g: Geom, want_stats=False, act_after=None):
+    """With ``want_stats`` returns (y, stat_part or None) -- None when the geometry is not on the implicit-GEMM path.
+    ``act_after`` = (ACT_LEAKY, slope), only where _stem_bwd_form() holds: the output is the activated one."""
     data_layer = (_ACT_STORAGE == BF16 and x.dtype == torch.float32 and x.shape[-1] <= 4 and
                   mfull is None and r0 is None and denom is None)
     if data_layer and not _bf16_stem_form(x, w, g):
@@ -930,6 +990,9 @@ def pconv_dense(x, w, bias, mfull, r0, split, r1, denom, keep, inv, g: Geom, wan
         _no_masks("dense convolution", mfull, r0, r1, denom, keep)
         out = _dense_bf16(x, w, bias, g, want_stats)
         return (out, None) if (want_stats and not isinstance(out, tuple)) else out
+    if act_after is not None:        # K4s (_stem_bwd_form): the LeakyReLU behind the stem belongs to the stem's node
+        assert act_after[0] == ACT_LEAKY and not want_stats and _stem_bwd_form(x, w, g)
+        return _StemS2DAct.apply(x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, float(act_after[1]))
     if _stem_form(x, w, g):
         out = _StemS2D.apply(x, w, bias, mfull, r0, r1, denom, keep, inv, split, g, want_stats)
     else:

@@ -58,9 +58,10 @@ class PartialConv(BaseModule):
         fc = self.feature_conv
         return ops.make_geom(fc.kernel_size, fc.stride, fc.padding, fc.dilation)
 
-    def forward_nhwc(self, x, mp, want_stats=False):
+    def forward_nhwc(self, x, mp, want_stats=False, act_after=None):
         """``x``: NHWC tensor or ops.LazyBN (a BatchNorm output still to be applied on load, K6b).  With
-        ``want_stats`` returns (y, mask, stat_part or None) for the BatchNorm that follows."""
+        ``want_stats`` returns (y, mask, stat_part or None) for the BatchNorm that follows.  ``act_after``: (code, slope) of the
+        LeakyReLU of a stem block (stem_act_block): y is then the activated output (K4s)."""
         fc = self.feature_conv
         w, b = fc.weight, fc.bias
         cin, cout, groups = fc.in_channels, fc.out_channels, fc.groups
@@ -108,7 +109,7 @@ class PartialConv(BaseModule):
                     if want_stats:
                         y, part = y
                 else:
-                    y = ops.pconv_dense(real(x), w, b, None, r0, split, r1, denom, keep, inv, g, want_stats=want_stats)
+                    y = ops.pconv_dense(real(x), w, b, None, r0, split, r1, denom, keep, inv, g, want_stats=want_stats, act_after=act_after)
                     if want_stats:
                         y, part = y
             else:
@@ -119,7 +120,7 @@ class PartialConv(BaseModule):
                     if want_stats:
                         y, part = y
                 else:
-                    y = ops.pconv_dense(real(x), w, b, mfull, None, 0, None, denom, keep, inv, g, want_stats=want_stats)
+                    y = ops.pconv_dense(real(x), w, b, mfull, None, 0, None, denom, keep, inv, g, want_stats=want_stats, act_after=act_after)
                     if want_stats:
                         y, part = y
         elif groups == cin == cout:
@@ -244,6 +245,16 @@ class DoubleUpSample(nn.Module):
 
     def forward(self, args):
         return _public_forward(self, args)
+
+
+def stem_act_block(layer, x):
+    """K4s: ``layer`` is a stem block -- [PartialConv in stem form (ops._stem_bwd_form), PartialActivation(LeakyReLU)], no BatchNorm --
+    over a plain NHWC tensor, and ops.FUSE_STEM_BWD is on: PartialConv.forward_nhwc(..., act_after=...) runs it as one node."""
+    if not (ops.FUSE_STEM_BWD and len(layer) == 2 and isinstance(layer[0], PartialConv) and isinstance(layer[1], PartialActivation)
+            and isinstance(x, torch.Tensor) and isinstance(layer[1].act_fn, nn.LeakyReLU)):
+        return False
+    fc = layer[0].feature_conv
+    return fc.groups == 1 and ops._stem_bwd_form(x, fc.weight, layer[0]._geom())
 
 
 def run_block(block, x, mp, allow_lazy=False, residual=None):
