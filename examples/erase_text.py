@@ -24,6 +24,8 @@ the polygon that is read back, not the rectangle.
 ``--crops HxW`` cuts every kept region's (with ``--group``: every block's) rotated rectangle out of the raw page on the device, deskewed and
 scaled into a slot of H x W pixels, and writes the first ``--max-crops N`` (default 64) as ``<name>_crop_NN.png``: what an OCR or translation
 step reads.  ``--crop-orient long`` lays vertical columns along the slot's width instead of keeping them upright.
+``--typeset-demo`` (needs ``--crops``) is the way back: each crop's number is rendered with PIL's built-in font, black on a transparent slot,
+and ``TextEraser.typeset`` lays the slots onto the cleaned page on the device, along the rectangles the crops came from: ``<name>_typeset.png``.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
 the scale it was trained at; the resize and the way back of the mask run on the device, the inpainting net keeps the page's pixels.
 ``--pack`` sends the inpainting net windows centred on the text regions instead of the grid's tiles, where that takes fewer of them: a
@@ -95,6 +97,7 @@ def main(argv=None):
     ap.add_argument("--crops", default=None, metavar="HxW", help="write every kept region's deskewed crop, fitted into H x W pixels, as <name>_crop_NN.png")
     ap.add_argument("--crop-orient", default="upright", choices=["upright", "long"], help="long: columns are laid along the crop's width")
     ap.add_argument("--max-crops", type=int, default=64, metavar="N", help="crops written per page with --crops")
+    ap.add_argument("--typeset-demo", action="store_true", help="with --crops: paste each crop's number back onto the cleaned page, as <name>_typeset.png")
     ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
@@ -121,6 +124,8 @@ def main(argv=None):
     ap.add_argument("--blend", action="store_true", help="seamless composition: correct the level of what the filler paints from its error around the holes")
     ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --blend (0..16)")
     args = ap.parse_args(argv)
+    if args.typeset_demo and args.crops is None:
+        ap.error("--typeset-demo needs --crops HxW")
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -152,7 +157,7 @@ def main(argv=None):
         out_folder = args.out_folder or args.img_folder
         os.makedirs(out_folder, exist_ok=True)
         names = sorted(f for f in os.listdir(args.img_folder) if f.lower().endswith(EXTENSIONS)
-                       and not f.endswith(("_clean.png", "_mask.png", "_boxes.png")))
+                       and not f.endswith(("_clean.png", "_mask.png", "_boxes.png", "_typeset.png")))
         pages = ((os.path.splitext(f)[0], np.asarray(Image.open(os.path.join(args.img_folder, f)).convert("RGB"))) for f in names)
     t0 = time.time()
     for name, page in pages:
@@ -165,6 +170,17 @@ def main(argv=None):
                 if found.info[r, 0]:
                     Image.fromarray(found.crop(r).cpu().numpy()).save(os.path.join(out_folder, "%s_crop_%02d.png" % (name, r)))
             print("%s: %d crops" % (name, len(found.info)))
+            if args.typeset_demo and len(found.info):                       # each row's number, black on a transparent slot, onto the cleaned page
+                from PIL import ImageDraw, ImageFont
+                font = ImageFont.load_default()
+                slots = np.zeros((len(found.info), *eraser.crops, 4), np.uint8)
+                for r in range(len(found.info)):
+                    uh, uw = int(found.info[r, 0]), int(found.info[r, 1])
+                    if uh and uw:
+                        label = Image.new("L", (uw, uh), 0)
+                        ImageDraw.Draw(label).text((1, 0), "%d" % r, fill=255, font=font)
+                        slots[r, :uh, :uw, 3] = np.asarray(label)           # the glyphs are the alpha plane; the colour stays black
+                Image.fromarray(eraser.typeset(clean, slots)).save(os.path.join(out_folder, name + "_typeset.png"))
         if args.boxes or args.geometry:
             from PIL import ImageDraw
             boxed = Image.fromarray(page)

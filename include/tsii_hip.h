@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 24
+#define TSII_ABI_VERSION 25
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -1165,6 +1165,51 @@ int tsii_region_geometry(const int* labels, const int* table, const int* n_regio
  * rect (8 bytes) or info (4 bytes). */
 int tsii_region_crops(const uint8_t* page, int h, int w, const int64_t* rect, const int* n_regions, int max_regions, int max_crops, int ch,
                       int cw, int orient, int fill, int max_ss, int* info, uint8_t* crops, void* stream);
+
+/* ---- K24: region paste (csrc/paste.hip) -- the return trip of K23: a batch of pictures, one per slot, is laid back onto the page along the
+ * rectangles the info rows name, antialiased and alpha-blended, on the device: what a typesetter does with the translated lettering.  All
+ * integer: one defined answer, the same bits on every run.
+ * page: uint8 [h,w,3], composited IN PLACE.  info: int32 [max_rows,10] exactly as tsii_region_crops leaves it, n_rows: int32 [1], both ON
+ * THE DEVICE (the call does not read them on the host), read only.  R = clamp(n_rows[0], 0, max_rows) rows are served.  slots: uint8
+ * [max_rows,ch,cw,4], straight (not premultiplied) RGBA, read only; the picture of row r is the slot's top-left uh x uw pixels, the rest of
+ * the slot is not read.  plan: int64 [max_rows,12], written by the call for the rows below R; the rows behind R are not touched.
+ *   Coordinates.  K23's: page pixel (y, x) has its centre at (4096 y, 4096 x), in units of 2^-12 pixel; with info[r] = (uh, uw, f, s', O_y,
+ *     O_x, SU_y, SU_x, SV_y, SV_x) the picture's area is O + a SU + b SV, a and b in [0, 1], and crop pixel (i, j) has its centre at
+ *     a = (2j + 1) / (2 uw), b = (2i + 1) / (2 uh).  f and s' are not used.
+ *   Plan, per row, in exact integers with floor divisions.  The row is DEAD -- plan[r] = 0, nothing is pasted -- if it fails the PLAN
+ *     VALIDATION below or its box is empty.  With S.T = S_y T_y + S_x T_x:
+ *       Gu_c = floor(SU_c uw 2^24 / (SU.SU)),  Gv_c = floor(SV_c uh 2^24 / (SV.SV))  per component c: the steps in crop pixels per 2^-12
+ *         page pixel, times 2^24.  SU and SV are treated as orthogonal, which they are up to the floors of K23's O, SU and SV: the
+ *         position along u is taken from the projection on SU alone.
+ *       s: the smallest number in 1..max_ss with s^2 (SU.SU) >= (4096 uw)^2 and s^2 (SV.SV) >= (4096 uh)^2, or max_ss where none has
+ *         both (unsigned 64-bit compares): about one crop pixel per page sub-sample at the most.
+ *       Box: per axis the smallest and the largest of the corners O, O + SU, O + SU + SV, O + SV, each >> 12, the lower end less 1 and the
+ *         upper end plus 1, clamped to the page: y0..y1, x0..x1 INCLUSIVE; empty if y0 > y1 or x0 > x1.
+ *       plan[r] = (1, y0, x0, y1, x1, s, Gu_y, Gu_x, Gv_y, Gv_x, 0, 0).
+ *   Pixels.  Page pixel (y, x) inside the box of a live row, sub-samples (l, m), l < s, m < s:
+ *       Pp_y = 4096 y + ((2l + 1) 2048) / s - 2048,  Pp_x = 4096 x + ((2m + 1) 2048) / s - 2048;  dP = Pp - O;
+ *       Qx = ((dP.Gu) >> 16) - 128,  Qy = ((dP.Gv) >> 16) - 128  (64-bit, arithmetic shifts): the position in 1/256 crop pixel;
+ *       j0 = Qx >> 8, fx = Qx & 255, i0 = Qy >> 8, fy = Qy & 255; the four neighbours (i0, i0 + 1) x (j0, j0 + 1) with the weights
+ *       w = (256 - fy | fy) (256 - fx | fx).  A neighbour outside uh x uw counts with alpha 0: transparent, not clamped to the edge, so the
+ *       picture's rim is antialiased.  With (c, a) the channel and the alpha byte of a neighbour:
+ *       Tc = (sum of w a c + 32768) >> 16 per channel,  Ta = (sum of w a + 32768) >> 16  (sum of w a c <= 65536 * 255 * 255 < 2^32 - 32768).
+ *     With N = s^2 and the sums over the pixel's sub-samples:  out = (sum Tc + page (255 N - sum Ta) + (255 N) / 2) / (255 N)  per channel,
+ *     32-bit unsigned; it never exceeds 255.  A pixel whose sum Ta is 0 is not written.  Pixels outside the box are not touched, also where
+ *     the rim of a much reduced picture would reach them.
+ *   Order.  The rows are composited in ascending r, `page` above being what the rows before left: a later row lies over an earlier one.
+ *     Every page pixel is stored at most once, by the one thread that owns it: no atomics, no race.
+ *   PLAN VALIDATION.  A row is dead unless 1 <= uh <= ch and 1 <= uw <= cw; |O_c| <= 2^29 and |SU_c|, |SV_c| <= 2^28 - 1; SU.SU >= 1 and
+ *     SV.SV >= 1; |SU_c| uw < 128 (SU.SU) and |SV_c| uh < 128 (SV.SV).  Then SU.SU < 2^57, every |G_c| < 2^31 and, a page coordinate being
+ *     below 2^27 + 2^11, every |dP_c| < 2^30: dP.G stays below 2^62 for every pixel of the box and its two products are 32 x 32 bits.
+ *     Every row tsii_region_crops writes for a page of sides up to 32767 passes (a side of its rectangle is shorter than 2^28 units and at
+ *     least 4094 long, so |S_c| n / (S.S) <= 4096 / 4094).  The numerator SU_c uw 2^24 itself can leave int64 (2^28 * 2^12 * 2^24): the
+ *     kernel takes the quotient by long division, the result is the exact floor.  The count is clamped, every slot index is tested against
+ *     uh x uw and the box is clamped to the page: a foreign info gives wrong pictures, never an access outside the buffers.
+ * No workspace beyond plan, no allocation, no host synchronisation, no atomics, no floating point; everything on the caller's stream.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w outside 1..32767; ch or cw outside 1..4096; max_ss outside 1..4;
+ * max_rows < 1; a NULL pointer; a misaligned plan (8 bytes), info or n_rows (4 bytes). */
+int tsii_region_paste(uint8_t* page, int h, int w, const int* info, const int* n_rows, int max_rows, const uint8_t* slots, int ch, int cw,
+                      int max_ss, int64_t* plan, void* stream);
 
 #ifdef __cplusplus
 }

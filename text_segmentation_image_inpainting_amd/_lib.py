@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 24       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 25       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -208,6 +208,8 @@ SIGNATURES = {
     "tsii_region_geometry": (_i, [_p, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _z, _p]),
     # K23 region crops (csrc/crops.hip): uint8 page, int64 rectangles and int32 counts in, int32 info and uint8 slots out
     "tsii_region_crops": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
+    # K24 region paste (csrc/paste.hip): the uint8 page in place, int32 info and count and uint8 RGBA slots in, the int64 plan out
+    "tsii_region_paste": (_i, [_p, _i, _i, _p, _p, _i, _p, _i, _i, _i, _p, _p]),
 }
 
 _LIB = None

@@ -49,9 +49,9 @@ from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .fill import _seamless_fill, check_sweeps
 from .masks import MaskParts
-from .regions import (ReadBack, RegionCrops, _flat_regions, _region_crops, _region_geometry, _region_hulls, _region_seeds, _smooth_regions,
-                      _text_blocks, _text_regions, _tone_regions, check_block_args, check_crop_args, check_flat_args, check_geometry_args,
-                      check_region_args, check_seed_args, check_smooth_args, check_tone_args)
+from .regions import (ReadBack, RegionCrops, _check_int_range, _flat_regions, _region_crops, _region_geometry, _region_hulls, _region_paste,
+                      _region_seeds, _rgba, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args, check_crop_args,
+                      check_flat_args, check_geometry_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
 
 
 class TileGrid(NamedTuple):
@@ -517,6 +517,8 @@ class TextEraser:
         self.last_regions = None                        # its regions (regions path only): the ``last_regions`` keys of the class docstring
         self.last_labels = None                         # its int32 label plane, left on the device
         self.last_crops = None                          # its crops (``crops`` only): uint8 ``[max_crops, ch, cw, 3]``, left on the device
+        self.last_crop_info = None                      # their info, int32 ``[max_crops * 10]``, and (``_crop_rows``) the word of the row count, left on the device: what ``typeset`` reads
+        self._crop_rows = self._crop_page = None
         self.last_route_labels = None                   # the int32 label plane the flat, smooth and tone stages worked on, left on the device; None unless one of them is enabled
 
     # A page runs in three phases over one PageState: _enqueue, _read_back (the one synchronisation) and _finish with _download behind
@@ -661,6 +663,7 @@ class TextEraser:
         if self.crops is not None:                      # of the RAW page: the lettering is what is wanted; on the rectangles of the geometry stage
             self.last_crops, info = _region_crops(st.page_d, geometry[lay.geometry.rect], first[lay.n_regions], self.max_regions, self.crops,
                                                   self.max_crops, self.crop_orient, self.crop_fill, self.crop_supersample)
+            self.last_crop_info, self._crop_rows, self._crop_page = info, first[lay.n_regions][1:], (g.h, g.w)
             self._mark("crops")
         st.read_back = lay.join(first, second, whole, geometry, info)
 
@@ -753,4 +756,30 @@ class TextEraser:
         if isinstance(page, (list, tuple)):
             return [self._erase(p) for p in page]
         return self._erase(page)
+
+    def typeset(self, page_u8, slots, supersample=4):
+        """Lay ``slots`` -- pictures drawn into the slots of the latest page's crops, ``[n <= max_crops, ch, cw, 4]`` uint8 straight RGBA, or
+        ``[..., 3]``, which is opaque; numpy or torch, host or device -- onto ``page_u8`` (``[H, W, 3]`` uint8, normally the ``clean`` the call
+        just returned) where the crops were cut out: the page with its new lettering.  ``page_u8`` is not modified; the result is a copy of
+        the same kind, on the same device.  Row ``r`` goes where ``last_regions["crops"]`` says slot ``r`` came from, a later row over an
+        earlier one, rows without a crop paste nothing and no slots give the copy; antialiased, with up to ``supersample`` (1..4) squared sub-samples per page pixel
+        (``paste_crops``, "K24: region paste").  The ``info`` of the crops stage is still on the device: nothing is uploaded but the slots (and
+        a host page), and nothing is read back.  A call of its own behind ``__call__``: the page's course is not touched."""
+        if self.crops is None:
+            raise RuntimeError("typeset needs the crops stage: TextEraser(crops=(ch, cw))")
+        if self.last_crop_info is None:
+            raise RuntimeError("typeset needs a page: no page has been erased yet")
+        p = _page_tensor(page_u8)
+        sl = torch.from_numpy(np.ascontiguousarray(slots)) if isinstance(slots, np.ndarray) else slots
+        if (not isinstance(sl, torch.Tensor) or sl.dtype != torch.uint8 or sl.dim() != 4 or sl.shape[0] > self.max_crops
+                or tuple(sl.shape[1:3]) != self.crops or sl.shape[3] not in (3, 4)):
+            raise ValueError(f"slots must be [0..{self.max_crops}, {self.crops[0]}, {self.crops[1]}, 3 or 4] uint8, got "
+                             f"{tuple(sl.shape) if isinstance(sl, torch.Tensor) else type(sl)} {getattr(sl, 'dtype', '')}")
+        _check_int_range("supersample", supersample, 1, 4)
+        if tuple(p.shape[:2]) != self._crop_page:
+            raise ValueError(f"page of {tuple(p.shape[:2])} pixels; the crops are those of a page of {self._crop_page}")
+        out = p.to(self.device, copy=True).contiguous()
+        if sl.shape[0] > 0:                             # no slots: the copy, as paste_crops has it
+            _region_paste(out, self.last_crop_info, self._crop_rows, _rgba(sl.to(self.device)), supersample)
+        return out.cpu().numpy() if isinstance(page_u8, np.ndarray) else out.to(page_u8.device)
 

@@ -36,6 +36,10 @@ region geometry"): the oriented box a translation is typeset into, and the text 
 
 ``region_crops`` cuts every such rectangle out of the page, deskewed and scaled into a fixed slot, and leaves the batch on the device
 (``tsii_region_crops``, ``csrc/crops.hip``; "K23: region crops"): the picture an OCR net or a reviewer starts from.
+
+``paste_crops`` is the way back: a batch of RGBA pictures, one per slot, is laid onto a page along the rectangles the crops' ``info`` names,
+antialiased and alpha-blended in row order (``tsii_region_paste``, ``csrc/paste.hip``; "K24: region paste"): the translated lettering on the
+cleaned page.
 """
 from typing import NamedTuple
 
@@ -212,6 +216,10 @@ class RegionCrops(NamedTuple):
         """(along u, along v): page pixels per crop pixel along the crop's x and y axes; below 1 where the block was magnified"""
         uh, uw = int(self.info[r, 0]), int(self.info[r, 1])
         return float(np.hypot(*self.info[r, 6:8].astype(np.float64))) / 4096.0 / uw, float(np.hypot(*self.info[r, 8:10].astype(np.float64))) / 4096.0 / uh
+
+    def paste(self, page_u8, slots, **kw):
+        """``paste_crops(page_u8, slots, self.info, **kw)``: pictures drawn into these slots, laid back where the crops came from"""
+        return paste_crops(page_u8, slots, self.info, **kw)
 
 
 CROP_ORIENTS = {"upright": 0, "long": 1}
@@ -528,6 +536,48 @@ def _region_crops(page, rect, n_regions, max_regions, size, max_crops, orient, f
     call("tsii_region_crops", ptr(page), h, w, ptr(rect), ptr(n_regions), int(max_regions), int(max_crops), ch, cw, CROP_ORIENTS[orient], int(fill),
          int(supersample), ptr(info), ptr(crops), _lib.stream())
     return crops, info
+
+
+def check_paste_args(slots_shape, info_shape, n_rows, supersample):
+    """the shapes of ``paste_crops``: slots ``[n, ch, cw, 3 | 4]`` with sides 1..4096, info ``[n, 10]`` of the same ``n``, ``n_rows`` (None: all)
+    in ``0..n`` -> the rows to serve"""
+    slots_shape, info_shape = tuple(int(v) for v in slots_shape), tuple(int(v) for v in info_shape)
+    if len(slots_shape) != 4 or slots_shape[3] not in (3, 4):
+        raise ValueError(f"slots must be [n, ch, cw, 3 or 4] uint8, got {slots_shape}")
+    if slots_shape[0] > 0:
+        _check_int_range("slots height", slots_shape[1], 1, 4096)
+        _check_int_range("slots width", slots_shape[2], 1, 4096)
+    if len(info_shape) != 2 or info_shape[1] != CROP_INFO or info_shape[0] != slots_shape[0]:
+        raise ValueError(f"info must be [n, {CROP_INFO}] int32 with a row per slot, got {info_shape} for slots of {slots_shape}")
+    n = slots_shape[0] if n_rows is None else n_rows
+    _check_int_range("n_rows", n, 0, slots_shape[0])
+    _check_int_range("supersample", supersample, 1, 4)
+    return int(n)
+
+
+PASTE_PLAN = 12                                             # int64 words of plan per row
+
+
+def _region_paste(page, info_d, n_d, slots, max_ss):
+    """``tsii_region_paste`` on the current stream: ``page`` (uint8 ``[h, w, 3]``, on the device) is composited IN PLACE with ``slots`` (uint8
+    ``[max_rows, ch, cw, 4]``, straight RGBA) along ``info_d`` (the device words of ``_region_crops``' info, ``10 * max_rows`` of them at
+    least); ``n_d``: the device word of the row count -> plan int64 ``[max_rows, 12]`` on the device (row ``r``: live, the box ``y0, x0, y1,
+    x1`` inclusive, the sub-samples per axis, the steps)."""
+    h, w = int(page.shape[0]), int(page.shape[1])
+    max_rows, ch, cw = int(slots.shape[0]), int(slots.shape[1]), int(slots.shape[2])
+    assert page.dtype == torch.uint8 and page.is_contiguous() and page.dim() == 3 and page.shape[2] == 3
+    assert slots.dtype == torch.uint8 and slots.is_contiguous() and slots.dim() == 4 and slots.shape[3] == 4 and slots.device == page.device
+    assert info_d.dtype == torch.int32 and info_d.is_contiguous() and info_d.numel() >= CROP_INFO * max_rows and n_d.dtype == torch.int32
+    plan = torch.zeros((max_rows, PASTE_PLAN), dtype=torch.int64, device=page.device)
+    call("tsii_region_paste", ptr(page), h, w, ptr(info_d), ptr(n_d), max_rows, ptr(slots), ch, cw, int(max_ss), ptr(plan), _lib.stream())
+    return plan
+
+
+def _rgba(slots):
+    """device slots ``[n, ch, cw, 3 | 4]`` -> contiguous RGBA: three channels are opaque"""
+    if slots.shape[3] == 4:
+        return slots.contiguous()
+    return torch.cat([slots, torch.full_like(slots[..., :1], 255)], dim=3)
 
 
 def _region_seeds(text, labels, seed, packed, room, max_regions, min_seeds, members=None, grid=None):
@@ -872,6 +922,31 @@ def region_crops(page_u8, rect, size, n_rows=None, orient="upright", fill=255, s
     count = torch.tensor([n, n], dtype=torch.int32, device=dev)
     crops, info = _region_crops(p.to(dev).contiguous(), rect_d, count, len(rows), size, n, orient, fill, supersample)
     return RegionCrops(_like(crops, page_u8), info.cpu().numpy().reshape(n, CROP_INFO))
+
+
+def paste_crops(page_u8, slots, info, n_rows=None, supersample=4, device=None):
+    """Pictures laid back onto a page where ``region_crops`` cut them out: the return trip a typesetter needs.  ``page_u8``: ``[H, W, 3]``
+    uint8, numpy or torch, host or device, sides up to 32767; it is not modified, the result is a copy of the same kind and on the same
+    device.  ``slots``: ``[n, ch, cw, 4]`` uint8, straight (not premultiplied) RGBA, or ``[n, ch, cw, 3]``, which is opaque; the picture of row
+    ``r`` is its top-left ``uh x uw`` pixels, the rest of the slot is ignored.  ``info``: ``[n, 10]`` int32, numpy or torch: ``RegionCrops.info``
+    (or the device tensor behind it), which says where each slot came from.  The first ``n_rows`` rows (default: all) are pasted in
+    ascending order, a later one over an earlier one; rows without pixels paste nothing.  Bilinear in integers, with up to ``supersample``
+    (1..4) squared sub-samples per page pixel where the picture is reduced; the picture's rim is antialiased against the page.  No
+    synchronisation beyond the copies of a host page.  A host page is worked on on ``device`` (default ``cuda:0``)."""
+    p = torch.from_numpy(np.ascontiguousarray(page_u8)) if isinstance(page_u8, np.ndarray) else page_u8
+    if p.dim() != 3 or p.dtype != torch.uint8 or p.shape[2] != 3 or not 1 <= p.shape[0] <= 32767 or not 1 <= p.shape[1] <= 32767:
+        raise ValueError(f"page must be [H, W, 3] uint8 with sides 1..32767, got {tuple(p.shape)} {p.dtype}")
+    sl = torch.from_numpy(np.ascontiguousarray(slots)) if isinstance(slots, np.ndarray) else slots
+    rows = torch.from_numpy(np.ascontiguousarray(info)) if isinstance(info, np.ndarray) else info
+    if sl.dtype != torch.uint8 or rows.dtype != torch.int32:
+        raise ValueError(f"slots must be uint8 and info int32, got {sl.dtype} and {rows.dtype}")
+    n = check_paste_args(sl.shape, rows.shape, n_rows, supersample)
+    dev = torch.device(device) if device is not None else (p.device if p.is_cuda else torch.device("cuda:0"))
+    out = p.to(dev, copy=True).contiguous()
+    if n > 0:
+        count = torch.tensor([n], dtype=torch.int32, device=dev)
+        _region_paste(out, rows.to(dev).contiguous().reshape(-1), count, _rgba(sl.to(dev)), supersample)
+    return _like(out, page_u8)
 
 
 def text_regions(text, connectivity=8, min_area=0, max_regions=4096, device=None) -> TextRegions:

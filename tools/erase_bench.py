@@ -68,6 +68,10 @@ grows the read-back, so ``geometry_ab`` runs the whole page with and without it,
 into a slot of H x W pixels, behind the flat / smooth / tone stages) with its own pair of events; ``regions`` then reports ``crops`` (rows
 served), ``crop_pixels`` (their pixels) and ``crop_subsamples`` (the bilinear samples behind them).  ``crops_ab`` runs the whole page with
 and without it, alternating, in the same process, as ``geometry_ab`` does.
+``--typeset`` (needs ``--crops``) times ``TextEraser.typeset`` behind the page, with the page's own crops as opaque slots: ``typeset`` reports
+``call_ms`` (HIP events around the whole call on a device page: the copy of the page, the alpha plane and tsii_region_paste), ``kernels_ms``
+(events around tsii_region_paste alone; compare with the ``crops`` stage of the same run), ``page_ms`` (the page on the host clock without and
+with the call, alternating), ``rows`` (pasted), ``box_pixels`` (page pixels visited), ``subsamples`` and ``pixels_changed``.
 
 ``--blend`` adds the ``blend`` stage (tsii_seamless_fill on the filler's tiles or windows, between the filler and compose) with its own pair
 of events.  Compare with the same line without ``--blend`` in the same session, and with ``--filler harmonic``, whose filler stage is the
@@ -163,6 +167,7 @@ def main(argv=None):
     ap.add_argument("--crops", default=None, metavar="HxW", help="time the crops stage (tsii_region_crops) into slots of H x W pixels; turns --geometry on")
     ap.add_argument("--crop-orient", default="upright", choices=["upright", "long"])
     ap.add_argument("--max-crops", type=int, default=64, metavar="N", help="slots with --crops")
+    ap.add_argument("--typeset", action="store_true", help="time TextEraser.typeset (tsii_region_paste) with the page's own crops as opaque slots; needs --crops")
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
     ap.add_argument("--pack", action="store_true", help="windows on the text regions instead of the grid's tiles (turns the regions stage on)")
@@ -189,6 +194,8 @@ def main(argv=None):
     ap.add_argument("--blend", action="store_true", help="time the blend stage (tsii_seamless_fill) between the filler and compose")
     ap.add_argument("--blend-sweeps", type=int, default=8, metavar="N", help="Jacobi sweeps per level of --blend (0..16)")
     args = ap.parse_args(argv)
+    if args.typeset and args.crops is None:
+        ap.error("--typeset needs --crops HxW")
     import text_segmentation_image_inpainting_amd as T
     from text_segmentation_image_inpainting_amd import pipeline as P
     from text_segmentation_image_inpainting_amd import regions as RG
@@ -514,6 +521,41 @@ def main(argv=None):
         crops_ab = {"page_ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in vals.items()},
                     "d2h_int32_words": words, "slots": [args.max_crops, *crop_size], "orient": args.crop_orient}
 
+    typeset = None
+    if args.typeset:                                        # the way back: the page's own crops, opaque, laid onto the cleaned page (tsii_region_paste)
+        from text_segmentation_image_inpainting_amd import _lib
+        er = make(True)
+        clean_d = torch.from_numpy(er(page)[0]).to(dev)
+        slots = er.last_crops
+        events, host = [], {"with": [], "without": []}
+        _lib.start_timing(["tsii_region_paste"])
+        for i in range(args.warmup + args.repeats):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            out_d = er.typeset(clean_d, slots)              # a device page in: the copy of the page, the alpha plane and the two kernels
+            e1.record()
+            if i >= args.warmup:
+                events.append((e0, e1))
+        kernels = [v[0] for v in _lib.stop_timing()["tsii_region_paste"]][args.warmup:]
+        call_ms = [a.elapsed_time(b) for a, b in events]
+        for i in range(args.warmup + args.repeats):        # the page on the host clock without and with the call, alternating
+            for k in ("without", "with"):
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                clean_h = er(page)[0]
+                if k == "with":
+                    er.typeset(clean_h, slots)
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    host[k].append((time.perf_counter() - t0) * 1e3)
+        plan = RG._region_paste(clean_d.clone(), er.last_crop_info, er._crop_rows, RG._rgba(slots), 4).cpu().numpy()
+        live = plan[plan[:, 0] != 0]
+        box = (live[:, 3] - live[:, 1] + 1) * (live[:, 4] - live[:, 2] + 1)
+        spread = lambda v: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)}
+        typeset = {"call_ms": spread(call_ms), "kernels_ms": spread(kernels), "page_ms": {k: spread(v) for k, v in host.items()},
+                   "rows": int(len(live)), "box_pixels": int(box.sum()), "subsamples": int((box * live[:, 5] ** 2).sum()),
+                   "pixels_changed": int((out_d != clean_d).any(dim=-1).sum()), "slots": [args.max_crops, *crop_size]}
+
     result = {
         "tool": "erase_bench", "page": [h, w], "tile": args.tile, "halo": args.halo, "dilate": args.dilate, "tile_batch": args.tile_batch,
         "seg_model": args.seg_model, "fill_model": args.fill_model if args.filler == "net" else repr(fil), "filler": args.filler,
@@ -534,7 +576,7 @@ def main(argv=None):
         "tones": args.tones, "tone": args.tone, "tone_ring": args.tone_ring if with_tone else None,
         "tone_period": args.tone_period if with_tone else None,
         "blend": args.blend, "blend_sweeps": args.blend_sweeps if args.blend else None, "blend_split_ms": blend_split,
-        "geometry": args.geometry, "geometry_ab": geometry_ab, "crops": args.crops, "crops_ab": crops_ab,
+        "geometry": args.geometry, "geometry_ab": geometry_ab, "crops": args.crops, "crops_ab": crops_ab, "typeset": typeset,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
