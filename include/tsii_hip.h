@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 25
+#define TSII_ABI_VERSION 26
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -123,6 +123,19 @@ size_t tsii_pw_bwd_dxdw_ws_bytes(int64_t m, int n, int k);
 int tsii_pw_bwd_dxdw(const float* dy, const float* x, int64_t m, int n, const float* w, int k, const float* inv,
                      const float* keep, const float* r0, int split, const float* r1, float* dx, float* dw, float* dbias,
                      void* ws, size_t ws_bytes, void* stream);
+/* K3xb: tsii_bn_bwd_apply + tsii_pw_bwd_dxdw in one pass, without the dy tensor between them.  da [m, n]: the gradient w.r.t. the
+ * output of the BatchNorm(+act) that follows the layer; y [m, n]: that BatchNorm's raw input (the layer's output); coef [6][n]: the
+ * table tsii_bn_bwd_reduce leaves; act / slope: a load-time activation (none, ReLU, ReLU6, LeakyReLU with slope in [0, 1]).  The kernel
+ * forms g = dy * inv with dy the very bits tsii_bn_bwd_apply would write, and is K3x from there on: dx and dw equal those of the two
+ * calls bit for bit.  dbias must be NULL (a 1x1 layer in front of a BatchNorm has no bias; layers with one keep the two calls); keep
+ * is accepted for symmetry and not read.  Shapes: tsii_pw_bwd_dxdw_bn_ok(m, n, k, 0): as K3x with k <= 64 and n <= 256; min_m < 0:
+ * the measured class only, k == 64, n == 256, m >= 524288.  da, y, x, ws 16-byte aligned; ws: tsii_pw_bwd_dxdw_bn_ws_bytes. */
+int tsii_pw_bwd_dxdw_bn_ok(int64_t m, int n, int k, int64_t min_m);
+int tsii_pw_bwd_dxdw_bn_tiles_per_block(int64_t m, int n, int k);
+size_t tsii_pw_bwd_dxdw_bn_ws_bytes(int64_t m, int n, int k);
+int tsii_pw_bwd_dxdw_bn(const float* da, const float* y, const float* coef, int act, float slope, const float* x, int64_t m, int n,
+                        const float* w, int k, const float* inv, const float* keep, const float* r0, int split, const float* r1,
+                        float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, void* stream);
 
 /* ---- K2: depth-wise partial convolution (PartialConv groups=C, MobileNetV2.py:174-176) --
  *   y[n,ho,wo,c] = keep ? (sum_taps w[c,t]*x[n,hi,wi,c]*rmask[n,hi,wi]) / denom[n,ho,wo] + b[c] : 0

@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 25       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 26       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -34,6 +34,10 @@ SIGNATURES = {
     "tsii_pw_bwd_dxdw_tiles_per_block": (_i, [_l, _i, _i]),
     "tsii_pw_bwd_dxdw_ws_bytes": (_z, [_l, _i, _i]),
     "tsii_pw_bwd_dxdw": (_i, [_p, _p, _l, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
+    "tsii_pw_bwd_dxdw_bn_ok": (_i, [_l, _i, _i, _l]),
+    "tsii_pw_bwd_dxdw_bn_tiles_per_block": (_i, [_l, _i, _i]),
+    "tsii_pw_bwd_dxdw_bn_ws_bytes": (_z, [_l, _i, _i]),
+    "tsii_pw_bwd_dxdw_bn": (_i, [_p, _p, _p, _i, _f, _p, _l, _i, _p, _i, _p, _p, _p, _i, _p, _p, _p, _p, _p, _z, _p]),
     "tsii_dw_fwd": (_i, [_p, _p, _p, _p, _p, _p, _i, _i, _i, _i] + _GEOM + [_i, _i, _p, _p, _p]),
     "tsii_dw_bwd_dx": (_i, [_p, _p, _p, _p, _i, _i, _i, _i] + _GEOM + [_i, _i, _p, _p, _p]),
     "tsii_dw_bwd_dw_ws_bytes": (_z, [_i, _i, _i, _i, _i, _i]),

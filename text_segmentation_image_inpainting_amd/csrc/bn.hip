@@ -479,11 +479,8 @@ __global__ void bn_bwd_apply_kernel(const float* __restrict__ dout, const float*
         if (r0 + r >= M) break;
 #pragma unroll
         for (int i = 0; i < W; ++i) {
-            const float xh = (yv[r].v[i] - mu.v[i]) * istd.v[i];
-            const float z = xh * ga.v[i] + be.v[i];
-            float dz = dv[r].v[i] * act_grad(z, act, slope);
-            dz = dz - k1.v[i] - xh * k2.v[i];
-            dv[r].v[i] = dz * ga.v[i] * istd.v[i];
+            dv[r].v[i] = bn_bwd_elem(dv[r].v[i], yv[r].v[i], mu.v[i], istd.v[i], ga.v[i], be.v[i], k1.v[i], k2.v[i],
+                                     [&](float z) { return act_grad(z, act, slope); });
         }
         vstore_nt<W>(dy + (r0 + r) * C + c, dv[r]);
     }
@@ -524,11 +521,8 @@ __global__ void bn_bwd_apply_pool_kernel(const float* __restrict__ dout, const f
     for (int j = 0; j < 4; ++j) {
 #pragma unroll
         for (int i = 0; i < W; ++i) {
-            const float xh = (yv[j].v[i] - mu.v[i]) * istd.v[i];
-            const float z = xh * ga.v[i] + be.v[i];
-            float dz = dv[j].v[i] * act_grad(z, act, slope);
-            dz = dz - k1.v[i] - xh * k2.v[i];
-            dv[j].v[i] = dz * ga.v[i] * istd.v[i];
+            dv[j].v[i] = bn_bwd_elem(dv[j].v[i], yv[j].v[i], mu.v[i], istd.v[i], ga.v[i], be.v[i], k1.v[i], k2.v[i],
+                                     [&](float z) { return act_grad(z, act, slope); });
         }
         vstore_nt<W>(dy + pix[j] * C + c, dv[j]);
     }

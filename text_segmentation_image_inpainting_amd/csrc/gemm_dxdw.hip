@@ -14,6 +14,12 @@
 //   end       one partial [wide x thin] slab per block -> launch_reduce_rows; the bias gradient takes the column-sum route
 // Waves (4): dX tile rows 32 (w >> 1), thin tiles TT2 (w & 1) ..;  dW columns 32 (w >> 1) of the stage, the same thin tiles.
 // Registers (TT2 = 1, NST = 6: thin <= 64, wide <= 384): 96 dW + 16 dX accumulators, 16 (32 with x) in flight across the MFMA phase.
+//
+// K3xb (BN = true; TT2 = 1, NST = 4: thin <= 64, wide <= 256): the gradient operand is da, the gradient w.r.t. the OUTPUT of the
+// BatchNorm(+activation) that follows the layer, next to that BatchNorm's raw input y (= this layer's output).  Both stream in side
+// by side (16 more registers in flight, paid for by the 32 accumulators two stages fewer free) and the staging step forms
+// g = bn_bwd_elem(da, y, coef) * inv in the registers it splits anyway -- the stand-alone apply pass (bn.hip: bn_bwd_apply_kernel,
+// the same helper, the same bits) and its dy tensor are gone.  The constants' table coef[6][wide] sits in LDS, filled once per block.
 #include "bf16_common.h"
 #include "gemm_tiles.h"
 #include "split_bf16.h"
@@ -44,19 +50,51 @@ __device__ __forceinline__ void xw_store(unsigned char* __restrict__ S, const fl
     split_store<XW_ROWS, 3, true, false>(S, regs, col0, split, s0, s1, none, none, 1.f, 0.f, XW_ROWS, ncols);
 }
 
-template <int TT2, int NST>
+// K3xb operands: nothing in the plain forms (their code is what it was), the BatchNorm's side of the hand-over in the BN form
+template <bool BN>
+struct XwBn {};
+template <>
+struct XwBn<true> {
+    const float* y;      // [m, wide] raw BatchNorm input
+    const float* coef;   // [6][wide]: mean, 1/std, gamma, beta, sum dz / m, sum dz*xhat / m (tsii_bn_bwd_reduce)
+    float neg, hi;       // the activation in its load-time form (make_in_bn)
+};
+
+// g = BatchNorm-backward(da, y) of this thread's 8 columns (from `col` of the LDS table, CW columns per constant), in place
+template <int CW>
+__device__ __forceinline__ void xw_bn_apply(float4 (&da)[1][2], const float4 (&y)[1][2], const float* __restrict__ Cs, int col, float neg, float hi) {
+    // inbn_grad's values (bf16_common.h) as two selects: its `&&` became a branch per element here
+    auto grad = [&](float z) { const float in = z < hi ? 1.f : 0.f; return z > 0.f ? in : neg; };
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+        const float* c = Cs + col + 4 * q;
+        const float4 mu = *reinterpret_cast<const float4*>(c), is = *reinterpret_cast<const float4*>(c + CW);
+        const float4 ga = *reinterpret_cast<const float4*>(c + 2 * CW), be = *reinterpret_cast<const float4*>(c + 3 * CW);
+        const float4 k1 = *reinterpret_cast<const float4*>(c + 4 * CW), k2 = *reinterpret_cast<const float4*>(c + 5 * CW);
+        float4& d = da[0][q];
+        const float4& v = y[0][q];
+        d.x = bn_bwd_elem(d.x, v.x, mu.x, is.x, ga.x, be.x, k1.x, k2.x, grad);
+        d.y = bn_bwd_elem(d.y, v.y, mu.y, is.y, ga.y, be.y, k1.y, k2.y, grad);
+        d.z = bn_bwd_elem(d.z, v.z, mu.z, is.z, ga.z, be.z, k1.z, k2.z, grad);
+        d.w = bn_bwd_elem(d.w, v.w, mu.w, is.w, ga.w, be.w, k1.w, k2.w, grad);
+    }
+}
+
+template <int TT2, int NST, bool BN = false>
 __global__ __launch_bounds__(256, TT2 == 1 ? 2 : 1) void pw_dxdw_kernel(const float* __restrict__ dy, const float* __restrict__ x,
                                                                         const unsigned short* __restrict__ wt, const float* __restrict__ inv,
                                                                         RowScale rs, float* __restrict__ dx, float* __restrict__ part,
-                                                                        int ntiles, int tiles_per_block, int wide, int thin) {
+                                                                        int ntiles, int tiles_per_block, int wide, int thin, XwBn<BN> bn) {
+    constexpr int CW = 64 * NST;                         // columns of the constants' table (BN)
     constexpr int KP = 64 * TT2;                         // thin side as staged (2 TT2 tiles of 32)
     constexpr int WSUB = 3 * KP * 64;                    // bytes of a W^T sub-tile: 3 planes x KP rows x 32 bf16
     constexpr int WCH = KP / 64;                         // W^T chunks per thread, plane and sub-tile
-    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * XW_SUB + 2 * TT2 * XW_SUB + 2 * WSUB + 2 * XW_ROWS * 4];
+    __shared__ __attribute__((aligned(16))) unsigned char smem[2 * XW_SUB + 2 * TT2 * XW_SUB + 2 * WSUB + 2 * XW_ROWS * 4 + (BN ? 6 * CW * 4 : 0)];
     unsigned char* Gs = smem;                            // [2 column halves] sub-tiles of g
     unsigned char* Xs = Gs + 2 * XW_SUB;                 // [2 TT2 thin tiles] sub-tiles of x * rs
     unsigned char* Ws = Xs + 2 * TT2 * XW_SUB;           // [2 column halves][plane][KP rows k][32 n]
     float* Rs = reinterpret_cast<float*>(Ws + 2 * WSUB); // r0 | r1 of the tile's rows (dX epilogue)
+    float* Cs = Rs + 2 * XW_ROWS;                        // BN: coef[6][CW], zeros past `wide` (read behind the first stage's barrier)
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int li = lane & 31, hi = lane >> 5;
@@ -65,6 +103,13 @@ __global__ __launch_bounds__(256, TT2 == 1 ? 2 : 1) void pw_dxdw_kernel(const fl
     const int tile_beg = (int)blockIdx.x * tiles_per_block;
     const int tile_end = tile_beg + tiles_per_block < ntiles ? tile_beg + tiles_per_block : ntiles;
     const int64_t wplane = (int64_t)wide * thin;
+
+    if constexpr (BN) {
+        for (int i = threadIdx.x; i < 6 * CW; i += 256) {
+            const int j = i / CW, c = i - j * CW;
+            Cs[i] = c < wide ? bn.coef[j * wide + c] : 0.f;
+        }
+    }
 
     f32x16 adw[NST][TT2];
 #pragma unroll
@@ -75,7 +120,7 @@ __global__ __launch_bounds__(256, TT2 == 1 ? 2 : 1) void pw_dxdw_kernel(const fl
             for (int r = 0; r < 16; ++r) adw[s][t][r] = 0.f;
 
     // ---- what is in flight for the next stage: g (two sub-tiles), the W^T piece; at a tile's first stage x, inv and the mask rows
-    float4 rg[2][1][2], rx[2 * TT2][1][2];
+    float4 rg[2][1][2], rx[2 * TT2][1][2], ry[2][1][2];
     u32x4 rw[2][WCH][3];
     float finv = 1.f, fx0 = 1.f, fx1 = 1.f;
     auto prefetch = [&](int tile, int s, bool first, int wide, int thin) {
@@ -83,6 +128,11 @@ __global__ __launch_bounds__(256, TT2 == 1 ? 2 : 1) void pw_dxdw_kernel(const fl
         const float* gb = dy + row0 * wide;
 #pragma unroll
         for (int h = 0; h < 2; ++h) xw_load(gb, wide, 64 * s + 32 * h, wide, rg[h]);
+        if constexpr (BN) {
+            const float* yb = bn.y + row0 * wide;
+#pragma unroll
+            for (int h = 0; h < 2; ++h) xw_load(yb, wide, 64 * s + 32 * h, wide, ry[h]);
+        }
 
         if (first) {
             const float* xb = x + row0 * thin;
@@ -148,6 +198,8 @@ __global__ __launch_bounds__(256, TT2 == 1 ? 2 : 1) void pw_dxdw_kernel(const fl
                 __syncthreads();                         // the fragment reads of the previous stage (and its epilogue's Rs) are done
 #pragma unroll
                 for (int h = 0; h < 2; ++h) {
+                    // (columns past `wide` meet zero constants and are zeroed by the store; the table has a slot for every staged column)
+                    if constexpr (BN) xw_bn_apply<CW>(rg[h], ry[h], Cs, 64 * s + 32 * h + 8 * (tid & 3), bn.neg, bn.hi);
                     xw_store(Gs + h * XW_SUB, rg[h], 64 * s + 32 * h, wide, 0x7fffffff, finv, finv);
 #pragma unroll
                     for (int i = 0; i < WCH; ++i) {
@@ -248,14 +300,20 @@ __global__ __launch_bounds__(256, TT2 == 1 ? 2 : 1) void pw_dxdw_kernel(const fl
 
     // ---- the block's partial dw[n][k]: n = 64 s + 32 (w >> 1) + accumulator row, k = 32 u + li
     float* pz = part + (int64_t)blockIdx.x * wplane;
+    int li_e = li, hi_e = hi, wr_e = wr, wu_e = wu;
+    if constexpr (BN) {      // re-derived behind the loop: carried across it these indices were the form's only two spilled registers
+        unsigned t = threadIdx.x;
+        TSII_OPAQUE_U32(t);
+        li_e = (int)(t & 31u); hi_e = (int)((t >> 5) & 1u); wr_e = (int)(t >> 7); wu_e = (int)((t >> 6) & 1u);
+    }
 #pragma unroll
     for (int s = 0; s < NST; ++s)
 #pragma unroll
         for (int t = 0; t < TT2; ++t) {
-            const int k = (TT2 * wu + t) * 32 + li;
+            const int k = (TT2 * wu_e + t) * 32 + li_e;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
-                const int n = 64 * s + 32 * wr + (r & 3) + 8 * (r >> 2) + 4 * hi;
+                const int n = 64 * s + 32 * wr_e + (r & 3) + 8 * (r >> 2) + 4 * hi_e;
                 if (n < wide && k < thin) pz[n * thin + k] = adw[s][t][r];
             }
         }
@@ -267,6 +325,8 @@ static bool xw_shape_ok(int64_t m, int wide, int thin) {
     if (thin <= 64) return wide <= 384;
     return thin <= 128 && wide <= 192;
 }
+// K3xb: the one-thin-tile form with four column stages
+static bool xw_bn_shape_ok(int64_t m, int wide, int thin) { return xw_shape_ok(m, wide, thin) && thin <= 64 && wide <= 256; }
 
 // split-M plan: one full wave of blocks (2 per CU at thin <= 64, else 1), contiguous tile ranges
 static void xw_plan(int64_t m, int thin, int* nblocks, int* tiles_per_block) {
@@ -329,12 +389,66 @@ extern "C" int tsii_pw_bwd_dxdw(const float* dy, const float* x, int64_t m, int 
     if (rc) return rc;
     const RowScale rs = {r0, r1, r0 != nullptr ? split : 0};
     const int ntiles = (int)(m / XW_ROWS);
-    if (k <= 64) hipLaunchKernelGGL((pw_dxdw_kernel<1, 6>), dim3(nb), dim3(256), 0, st, dy, x, planes, inv, rs, dx, part, ntiles, tpb, n, k);
-    else hipLaunchKernelGGL((pw_dxdw_kernel<2, 3>), dim3(nb), dim3(256), 0, st, dy, x, planes, inv, rs, dx, part, ntiles, tpb, n, k);
+    if (k <= 64) hipLaunchKernelGGL((pw_dxdw_kernel<1, 6>), dim3(nb), dim3(256), 0, st, dy, x, planes, inv, rs, dx, part, ntiles, tpb, n, k, XwBn<false>{});
+    else hipLaunchKernelGGL((pw_dxdw_kernel<2, 3>), dim3(nb), dim3(256), 0, st, dy, x, planes, inv, rs, dx, part, ntiles, tpb, n, k, XwBn<false>{});
     rc = check_launch("pw_dxdw");
     if (rc) return rc;
     rc = launch_reduce_rows(part, nb, (int64_t)n * k, dw, st);
     if (rc) return rc;
     if (dbias != nullptr) rc = launch_colsum_scaled(dy, keep, m, n, dbias, cpart, st);
     return rc;
+}
+
+// ---- K3xb: the same with the backward APPLY pass of the BatchNorm(+activation) that follows the layer folded into the staging step
+extern "C" int tsii_pw_bwd_dxdw_bn_ok(int64_t m, int n, int k, int64_t min_m) {
+    if (gemm_products() != 6) return 0;
+    if (!xw_bn_shape_ok(m, n, k)) return 0;
+    if (min_m >= 0) return m >= min_m ? 1 : 0;
+    // the library's own choice: the class that was timed against apply pass + K3x
+    return (k == 64 && n == 256 && m >= TSII_DXDW_MIN_M) ? 1 : 0;
+}
+
+extern "C" int tsii_pw_bwd_dxdw_bn_tiles_per_block(int64_t m, int n, int k) {
+    if (!xw_bn_shape_ok(m, n, k)) return 0;
+    int nb = 0, tpb = 0;
+    xw_plan(m, k, &nb, &tpb);
+    return tpb;
+}
+
+extern "C" size_t tsii_pw_bwd_dxdw_bn_ws_bytes(int64_t m, int n, int k) {
+    if (!xw_bn_shape_ok(m, n, k)) return 0;
+    int nb = 0, tpb = 0;
+    xw_plan(m, k, &nb, &tpb);
+    return (size_t)nb * n * k * sizeof(float) + (size_t)3 * n * k * sizeof(unsigned short) + 16;
+}
+
+extern "C" int tsii_pw_bwd_dxdw_bn(const float* da, const float* y, const float* coef, int act, float slope, const float* x, int64_t m,
+                                   int n, const float* w, int k, const float* inv, const float* keep, const float* r0, int split,
+                                   const float* r1, float* dx, float* dw, float* dbias, void* ws, size_t ws_bytes, void* stream) {
+    TSII_REQUIRE(da && y && coef && x && w && dx && dw && ws, "pw_bwd_dxdw_bn: null pointer");
+    // dy is never written, so there is nothing to take a bias gradient from in a pass of its own; the layers this serves (a 1x1
+    // layer in front of a BatchNorm) have no bias.  keep only enters the bias gradient.
+    (void)keep;
+    TSII_REQUIRE(dbias == nullptr, "pw_bwd_dxdw_bn: layers with a bias keep tsii_bn_bwd_apply + tsii_pw_bwd_dxdw");
+    TSII_REQUIRE(gemm_products() == 6, "pw_bwd_dxdw_bn: the 6-product split-bf16 arithmetic only (tsii_set_gemm_products)");
+    TSII_REQUIRE(xw_bn_shape_ok(m, n, k), "pw_bwd_dxdw_bn: shape m=%lld n=%d k=%d is not eligible (tsii_pw_bwd_dxdw_bn_ok)", (long long)m, n, k);
+    InBN ib;
+    TSII_REQUIRE(make_in_bn(nullptr, nullptr, act, slope, &ib) == 0, "pw_bwd_dxdw_bn: activation %d (slope %g) has no load-time form", act, (double)slope);
+    TSII_REQUIRE(aligned16(da) && aligned16(y) && aligned16(x) && aligned16(ws), "pw_bwd_dxdw_bn: 16-byte aligned operands are required");
+    TSII_REQUIRE(ws_bytes >= tsii_pw_bwd_dxdw_bn_ws_bytes(m, n, k), "pw_bwd_dxdw_bn: workspace too small");
+    hipStream_t st = (hipStream_t)stream;
+    int nb = 0, tpb = 0;
+    xw_plan(m, k, &nb, &tpb);
+    float* part = (float*)ws;
+    unsigned short* planes = reinterpret_cast<unsigned short*>((reinterpret_cast<uintptr_t>(part + (size_t)nb * n * k) + 15) & ~(uintptr_t)15);
+    hipLaunchKernelGGL(split_w_kernel<3>, dim3(stream_grid((int64_t)n * k, 256)), dim3(256), 0, st, w, n, k, 1, planes);
+    int rc = check_launch("split_w");
+    if (rc) return rc;
+    const RowScale rs = {r0, r1, r0 != nullptr ? split : 0};
+    XwBn<true> bn;
+    bn.y = y; bn.coef = coef; bn.neg = ib.neg; bn.hi = ib.hi;
+    hipLaunchKernelGGL((pw_dxdw_kernel<1, 4, true>), dim3(nb), dim3(256), 0, st, da, x, planes, inv, rs, dx, part, (int)(m / XW_ROWS), tpb, n, k, bn);
+    rc = check_launch("pw_dxdw_bn");
+    if (rc) return rc;
+    return launch_reduce_rows(part, nb, (int64_t)n * k, dw, st);
 }

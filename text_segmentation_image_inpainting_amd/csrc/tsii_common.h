@@ -61,6 +61,22 @@ __device__ __forceinline__ float act_grad(float v, int act, float slope) {
     return 1.f;
 }
 
+// One element of the BatchNorm(+activation) backward APPLY pass: da (gradient w.r.t. act(BatchNorm(y))) and the raw y -> dy, with
+// the per-channel constants of coef[6][C] (mean, 1/std, gamma, beta, sum dz / m, sum dz*xhat / m; bn.hip).  `grad(z)` is the
+// activation's derivative at the pre-activation z.  ONE copy for the stand-alone pass (bn_bwd_apply_kernel) and the kernels that
+// apply it while they load (K3xb, gemm_dxdw.hip), with the roundings pinned -- z is one fused multiply-add, nothing else
+// contracts -- so that both give the same bits whatever each translation unit's compiler would have chosen around it.
+template <class G>
+__device__ __forceinline__ float bn_bwd_elem(float da, float y, float mu, float istd, float ga, float be, float k1, float k2, G grad) {
+#pragma clang fp contract(off)
+    const float xh = (y - mu) * istd;
+    const float z = __builtin_fmaf(xh, ga, be);
+    float dz = da * grad(z);
+    const float q = xh * k2;
+    dz = (dz - k1) - q;
+    return (dz * ga) * istd;
+}
+
 // K6b: BatchNorm(+ReLU-family activation) of the producer applied to an operand while it is loaded:
 //   z = sc[c]*v + sh[c];  a = min(max(z, neg*z), hi)      (4 VALU ops, branch-free, NaN propagates)
 //   NONE: neg 1, hi inf | RELU: 0, inf | LEAKY: slope in [0,1], inf | RELU6: 0, 6.   sc == nullptr: no transform.

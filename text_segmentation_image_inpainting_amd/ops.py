@@ -30,6 +30,10 @@ FUSE_DW_DXDW = True
 # eligible (tsii_pw_bwd_dxdw_ok: thin side <= 64 channels here, HBM-side row counts); everything else keeps the two calls
 FUSE_PW_DXDW = True
 PW_DXDW_MIN_M = -1      # rows from which K3x is taken; -1: the library's threshold (tests lower it to reach the kernel on small maps)
+# K3xb: ... and the backward APPLY pass of the BatchNorm that follows such a layer rides in that kernel's staging step
+# (tsii_pw_bwd_dxdw_bn, where tsii_pw_bwd_dxdw_bn_ok takes the shape): the BatchNorm's backward only reduces its K6c partial rows
+# (tsii_bn_bwd_reduce) and hands (gradient, raw input, constants) over, as for K6e below; dy is never written
+FUSE_PW_BN1_FOLD = True
 # K6e: ... and applies the backward of the BatchNorm that FOLLOWS the layer while it loads (tsii_dw_bwd_dxdw_bn2): that BatchNorm's
 # backward only reduces its K6c partial rows (tsii_bn_bwd_reduce) and hands (gradient, raw input, constants) over; stride 1
 FUSE_DW_BN2_FOLD = True
@@ -211,18 +215,23 @@ class _FoldHandOver:
     """K6e hand-over: the BatchNorm that follows a depth-wise layer defers its backward APPLY pass to that layer's dX + dW kernel, which
     forms dy = BatchNorm-backward(da, y) while it stages its slab.  _BNLazy.backward leaves (da, y, coef, act, slope) here and returns da
     unchanged as the "gradient" of the conv output; _Depthwise.backward takes it if the gradient it receives is that very tensor --
-    anything else (autograd summed a second consumer's gradient into it) cannot be undone and raises."""
+    anything else (autograd summed a second consumer's gradient into it) cannot be undone and raises.
+    K3xb: the same between a thin 1x1 layer (``thin``: its input channels) and the BatchNorm behind it."""
 
-    __slots__ = ("pending",)
+    __slots__ = ("pending", "thin")
 
-    def __init__(self):
+    def __init__(self, thin=None):
         self.pending = None
+        self.thin = thin        # None: a depth-wise layer's hand-over (K6e)
 
     def take(self, gy):
         pend, self.pending = self.pending, None
         if pend is None:
             return None
         if pend[0].data_ptr() != gy.data_ptr() or pend[0].shape != gy.shape:
+            if self.thin is not None:
+                raise RuntimeError("deferred BatchNorm backward (K3xb): the 1x1 layer's output has another consumer than its BatchNorm; "
+                                   "set ops.FUSE_PW_BN1_FOLD = False for this network")
             raise RuntimeError("deferred BatchNorm backward (K6e): the depth-wise layer's output has another consumer than its BatchNorm; "
                                "set ops.FUSE_DW_BN2_FOLD = False for this network")
         return pend
@@ -235,6 +244,15 @@ def _apply_deferred_bn(pend):
     dy = torch.empty_like(y)
     call("tsii_bn_bwd_apply", ptr(da), ptr(y), y.numel() // c, c, ptr(coef), int(act), float(slope), ptr(dy), _lib.stream())
     return dy
+
+
+def _pw_bn_fold_ok(m, cout, k) -> bool:
+    """K3xb takes this layer: the library's answer at the row threshold in force.  A lowered PW_DXDW_MIN_M lowers ROWS only -- the layer
+    class (thin and wide side) stays the one the library takes by its own choice, so small maps reach the kernel and other layers keep K3x."""
+    L = _lib.lib()
+    if not L.tsii_pw_bwd_dxdw_bn_ok(m, cout, k, int(PW_DXDW_MIN_M)):
+        return False
+    return PW_DXDW_MIN_M < 0 or bool(L.tsii_pw_bwd_dxdw_bn_ok(1 << 30, cout, k, -1))
 
 
 class _Pointwise(torch.autograd.Function):
@@ -295,6 +313,13 @@ class _Pointwise(torch.autograd.Function):
         ctx.save_for_backward(x, w, r0, r1, inv, keep, in_scale, in_shift)
         ctx.split, ctx.has_bias, ctx.in_cfg = int(split), bias is not None, (int(in_act), float(in_slope))
         ctx.set_materialize_grads(False)   # no zero tensors for the statistics output (one tiny fill kernel each otherwise)
+        # K3xb: will this layer's backward be the one-pass dX + dW kernel in the form that applies the FOLLOWING BatchNorm's backward
+        # while it stages the gradient?  Decided here, as for K6e; pconv_pointwise hangs the hand-over on y
+        ctx.fold = None
+        if (FUSE_PW_BN1_FOLD and FUSE_PW_DXDW and bias is None and in_scale is None and bn is None and up_add is None
+                and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and _al16(x, y)
+                and _pw_bn_fold_ok(m, cout, k)):
+            ctx.fold = _FoldHandOver(thin=k)
         if want_stats:
             ctx.mark_non_differentiable(part)
             return y, part
@@ -338,6 +363,21 @@ class _Pointwise(torch.autograd.Function):
                      ptr(dw), ptr(db), ptr(ws), nbytes, st)
             return (dx, dw, db) + (None,) * 13
         want_w = ctx.needs_input_grad[1] or (ctx.has_bias and ctx.needs_input_grad[2])
+        pend = ctx.fold.take(gy) if getattr(ctx, "fold", None) is not None else None
+        if pend is not None:
+            # the following BatchNorm deferred its apply pass to this backward (K3xb); if the one-pass kernel cannot run after all (a
+            # switch changed between forward and backward), the stand-alone apply pass runs here and today's path continues
+            _, y1, coef, act1, slope1 = pend
+            if (FUSE_PW_BN1_FOLD and FUSE_PW_DXDW and ctx.needs_input_grad[0] and ctx.needs_input_grad[1] and not ctx.has_bias
+                    and in_scale is None and ctx.bn is None and not ctx.has_up and load_time_act(act1, slope1) and _al16(gy, y1, x)
+                    and _pw_bn_fold_ok(m, cout, k)):
+                dx, dw = torch.empty_like(x), torch.empty_like(w)
+                nbytes = _lib.lib().tsii_pw_bwd_dxdw_bn_ws_bytes(m, cout, k)
+                ws = _ws(nbytes, x)
+                call("tsii_pw_bwd_dxdw_bn", ptr(gy), ptr(y1), ptr(coef), int(act1), float(slope1), ptr(x), m, cout, ptr(w), k, ptr(inv),
+                     ptr(keep), ptr(r0), ctx.split, ptr(r1), ptr(dx), ptr(dw), None, ptr(ws), nbytes, st)
+                return (dx, dw, None) + (None,) * 13
+            gy, pend = _apply_deferred_bn(pend), None
         if (FUSE_PW_DXDW and ctx.needs_input_grad[0] and want_w and in_scale is None and ctx.bn is None
                 and _lib.lib().tsii_pw_bwd_dxdw_ok(m, cout, k, int(PW_DXDW_MIN_M)) and _al16(gy, x)):
             # K3x.  (A K7b layer comes here too: its dX and dW are these same two products, the addend's gradient below is untouched)
@@ -407,7 +447,12 @@ def pconv_pointwise(x, w, bias=None, r0=None, split=0, r1=None, denom=None, keep
             return _Pointwise.apply(x.token, w, bias, r0, r1, denom, keep, inv, split, x.scale, x.shift, x.act, x.slope,
                                     want_stats, bn)
         x = x.materialize()
-    return _Pointwise.apply(x, w, bias, r0, r1, denom, keep, inv, split, None, None, 0, 0.0, want_stats)
+    out = _Pointwise.apply(x, w, bias, r0, r1, denom, keep, inv, split, None, None, 0, 0.0, want_stats)
+    y = out[0] if want_stats else out
+    fold = getattr(y.grad_fn, "fold", None)
+    if fold is not None:
+        y._tsii_fold = fold      # read by bn_lazy: the BatchNorm over y may leave its backward apply pass to this layer's dX + dW kernel (K3xb)
+    return out
 
 
 # ---------------------------------------------------------------------------------------
@@ -1175,10 +1220,14 @@ class _BNLazy(torch.autograd.Function):
             return (dy, dgamma, dbeta) + (None,) * 11
         pool = ctx.pool
         fold = ctx.fold
-        if (fold is not None and part is not None and FUSE_DW_BN2_FOLD and load_time_act(act, slope) and c % 4 == 0 and _al16(ga, y)
+        if fold is not None and fold.thin is not None:      # K3xb: a thin 1x1 layer's hand-over
+            defer = FUSE_PW_BN1_FOLD and FUSE_PW_DXDW and _pw_bn_fold_ok(m, c, int(fold.thin))
+        else:
+            defer = fold is not None and FUSE_DW_BN2_FOLD
+        if (defer and part is not None and load_time_act(act, slope) and c % 4 == 0 and _al16(ga, y)
                 and not (pool is not None and pool.want)):
-            # K6e: only the reduction of the K6c partial rows runs here (dgamma, dbeta, the constants' table); the apply pass rides in the
-            # producing depth-wise layer's dX + dW kernel, which receives ga itself
+            # K6e / K3xb: only the reduction of the K6c partial rows runs here (dgamma, dbeta, the constants' table); the apply pass rides
+            # in the producing layer's dX + dW kernel, which receives ga itself
             L = _lib.lib()
             coef = torch.empty((6, c), dtype=torch.float32, device=y.device)
             rbytes = L.tsii_bn_bwd_reduce_ws_bytes(part.shape[0], c)
