@@ -24,6 +24,9 @@ the polygon that is read back, not the rectangle.
 ``--crops HxW`` cuts every kept region's (with ``--group``: every block's) rotated rectangle out of the raw page on the device, deskewed and
 scaled into a slot of H x W pixels, and writes the first ``--max-crops N`` (default 64) as ``<name>_crop_NN.png``: what an OCR or translation
 step reads.  ``--crop-orient long`` lays vertical columns along the slot's width instead of keeping them upright.
+``--balloon T`` finds every kept region's (with ``--group``: every block's) speech balloon on the device -- the flood fill from the lettering over
+the colour around it, within T grey levels -- and draws its box and the largest upright rectangle inside it into ``<name>_boxes.png``;
+``--typeset-demo --into balloon`` then lays the slots into those rectangles instead of into the old lettering's boxes.
 ``--typeset-demo`` (needs ``--crops``) is the way back: each crop's number is rendered with PIL's built-in font, black on a transparent slot,
 and ``TextEraser.typeset`` lays the slots onto the cleaned page on the device, along the rectangles the crops came from: ``<name>_typeset.png``.
 ``--seg-long-side N`` (a multiple of 8; the reference's demo uses 600) lets the segmenter work on the page resized to a long side of N,
@@ -98,6 +101,12 @@ def main(argv=None):
     ap.add_argument("--crop-orient", default="upright", choices=["upright", "long"], help="long: columns are laid along the crop's width")
     ap.add_argument("--max-crops", type=int, default=64, metavar="N", help="crops written per page with --crops")
     ap.add_argument("--typeset-demo", action="store_true", help="with --crops: paste each crop's number back onto the cleaned page, as <name>_typeset.png")
+    ap.add_argument("--into", default="block", choices=["block", "balloon"], help="with --typeset-demo: lay the slots into the old lettering's box, or "
+                    "into the free rectangle of its speech balloon (needs --balloon)")
+    ap.add_argument("--balloon", type=int, default=None, metavar="T", help="find every region's speech balloon (the flood fill over the colour around it, "
+                    "within T grey levels) and draw its box and its inner rectangle into <name>_boxes.png")
+    ap.add_argument("--balloon-ring", type=int, default=3, metavar="N", help="width of the ring of surrounding pixels --balloon takes the colour from (1..8)")
+    ap.add_argument("--balloon-reach", type=int, default=256, metavar="N", help="pixels a balloon may reach beyond its lettering's box (ring..512)")
     ap.add_argument("--hull", action="store_true", help="fill the convex hull of every kept text region into the mask")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at this long side (multiple of 8), as EvaluateSet(resize=N)")
     ap.add_argument("--pack", action="store_true", help="inpaint windows centred on the text regions instead of the grid's tiles")
@@ -126,6 +135,8 @@ def main(argv=None):
     args = ap.parse_args(argv)
     if args.typeset_demo and args.crops is None:
         ap.error("--typeset-demo needs --crops HxW")
+    if args.into == "balloon" and args.balloon is None:
+        ap.error("--into balloon needs --balloon T")
     import text_segmentation_image_inpainting_amd as T
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
@@ -146,7 +157,7 @@ def main(argv=None):
                           tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend, blend_sweeps=args.blend_sweeps,
                           geometry=args.geometry, max_vertices=args.max_vertices,
                           crops=None if args.crops is None else tuple(int(v) for v in args.crops.lower().split("x")), max_crops=args.max_crops,
-                          crop_orient=args.crop_orient)
+                          crop_orient=args.crop_orient, balloon=args.balloon, balloon_ring=args.balloon_ring, balloon_reach=args.balloon_reach)
     if args.synthetic or args.img_folder is None:
         out_folder = args.out_folder or tempfile.mkdtemp(prefix="tsii_erase_")
         os.makedirs(out_folder, exist_ok=True)
@@ -176,12 +187,14 @@ def main(argv=None):
                 slots = np.zeros((len(found.info), *eraser.crops, 4), np.uint8)
                 for r in range(len(found.info)):
                     uh, uw = int(found.info[r, 0]), int(found.info[r, 1])
+                    if args.into == "balloon":                              # the slot is fitted to the balloon's rectangle, upright: draw into all of it
+                        uh, uw = eraser.crops
                     if uh and uw:
                         label = Image.new("L", (uw, uh), 0)
                         ImageDraw.Draw(label).text((1, 0), "%d" % r, fill=255, font=font)
                         slots[r, :uh, :uw, 3] = np.asarray(label)           # the glyphs are the alpha plane; the colour stays black
-                Image.fromarray(eraser.typeset(clean, slots)).save(os.path.join(out_folder, name + "_typeset.png"))
-        if args.boxes or args.geometry:
+                Image.fromarray(eraser.typeset(clean, slots, into=args.into)).save(os.path.join(out_folder, name + "_typeset.png"))
+        if args.boxes or args.geometry or args.balloon is not None:
             from PIL import ImageDraw
             boxed = Image.fromarray(page)
             draw = ImageDraw.Draw(boxed)
@@ -196,6 +209,13 @@ def main(argv=None):
                         draw.line(xy + xy[:1], fill=colour)
                 print("%s: %d oriented boxes, %d of them turned by more than 5 degrees" %
                       (name, len(geo.n_vertices), sum(5.0 < abs(geo.angle(r)) < 85.0 for r in range(len(geo.n_vertices)))))
+            if args.balloon is not None:                                   # the balloon's box (orange; dashed-looking where open) and the room inside it (magenta)
+                found = eraser.last_regions["balloons"]
+                for r in np.nonzero(found.is_balloon)[0]:
+                    (by0, bx0, by1, bx1), (ry0, rx0, ry1, rx1) = found.box[r].tolist(), found.inner[r].tolist()
+                    draw.rectangle([bx0, by0, bx1 - 1, by1 - 1], outline=(255, 200, 120) if found.is_open[r] else (255, 140, 0))
+                    draw.rectangle([rx0, ry0, rx1 - 1, ry1 - 1], outline=(255, 0, 255))
+                print("%s: %d balloons, %d of them open" % (name, eraser.last_stats["balloons"], eraser.last_stats["open_balloons"]))
             boxed.save(os.path.join(out_folder, name + "_boxes.png"))
         if args.boxes:
             if args.group is not None:

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define TSII_ABI_VERSION 26
+#define TSII_ABI_VERSION 27
 
 /* activation kinds for the BN/activation kernels */
 #define TSII_ACT_NONE 0
@@ -1223,6 +1223,51 @@ int tsii_region_crops(const uint8_t* page, int h, int w, const int64_t* rect, co
  * max_rows < 1; a NULL pointer; a misaligned plan (8 bytes), info or n_rows (4 bytes). */
 int tsii_region_paste(uint8_t* page, int h, int w, const int* info, const int* n_rows, int max_rows, const uint8_t* slots, int ch, int cw,
                       int max_ss, int64_t* plan, void* stream);
+
+/* ---- K25: region balloons (csrc/balloon.hip) -- the speech balloon around every table row's lettering: the flood fill from the row's own
+ * text over the colour that surrounds it, the balloon's area and box, whether it is closed, and the largest upright rectangle inside it
+ * around the block's centre, which is where a translation has room.  All integer: one defined answer, the same bits on every run.
+ * page: uint8 [h,w,3], read only.  text: uint8 [h,w], read only; a non-zero byte is text of some region.  labels int32 [h,w], table int32
+ * [max_regions,6] and n_regions int32 [2] as tsii_text_regions or tsii_text_blocks leave them, ON THE DEVICE (the call does not read them
+ * on the host), read only.  ring 1..8, tol 0..255, ring <= reach <= 512.  R = min(n_regions[1], max_regions) rows are served; for r < R:
+ *   Window.  W_r is the table row's box (y0, x0 inclusive, y1, x1 exclusive, each clamped to the page first), grown by `reach` on every
+ *     side and clipped to the page.  A side of W_r above 1024 pixels: status bit 8, every other word of the row 0.
+ *   Own pixels.  C_r: the pixels inside the clamped box with labels == table[r][0] and text != 0.  C_r empty: status bit 16, every other
+ *     word of the row 0.
+ *   Ring and colour (K13's).  Ring_r: the pixels with text == 0 within Chebyshev distance `ring` of a pixel of C_r (reach >= ring puts
+ *     them inside the window).  n, lo, hi and sum per channel over the ring's page bytes; colour = (2 sum + n) / (2 n), 0 where n == 0.
+ *     n == 0: status bit 1.  hi - lo > tol in any channel: status bit 2.  Either bit: there is no balloon -- status, n, the colour and the
+ *     anchor are reported, every other word of the row is 0.
+ *   Passable.  P_r = C_r + { p in W_r : text[p] == 0 and |page[p][c] - colour[c]| <= tol for c = 0, 1, 2 }.  The text of OTHER rows is an
+ *     obstacle: a second block in the same balloon is a hole in this one's.
+ *   Balloon.  B_r: the union of the 4-connected components of P_r, inside W_r, that hold a pixel of C_r.  area = |B_r|; (by0, bx0, by1,
+ *     bx1) its box, y1 and x1 exclusive.  OPEN, status bit 4: B_r has a pixel on a side of W_r that is not a side of the page -- the fill
+ *     ran to the end of its reach.  A balloon cut by the page's edge is closed.
+ *   Anchor.  (ay, ax): the pixel of C_r with the smallest |2y - (y0 + y1 - 1)| + |2x - (x0 + x1 - 1)|, ties to the smallest y, then the
+ *     smallest x.  It lies in B_r.
+ *   Rectangle.  For a row y with (y, ax) in B_r, L(y) and Rr(y) are the ends of the run of B_r through (y, ax).  The candidates are all
+ *     ya <= ay <= yb with (y, ax) in B_r for every y in ya..yb; width = min Rr - max L + 1 over those rows, area = (yb - ya + 1) * width.
+ *     The largest area wins, ties to the smallest ya, then the smallest yb.  (ry0, rx0, ry1, rx1) = (ya, max L, yb + 1, min Rr + 1).  Every
+ *     upright rectangle inside B_r that holds the anchor lies inside a candidate: this is the largest such rectangle.
+ *   balloon, int32 [max_regions,16]: balloon[r] = {status, n, colour r, g, b, area, by0, bx0, by1, bx1, ay, ax, ry0, rx0, ry1, rx1}.
+ *   rect, int64 [max_regions,8], K22's layout for the upright rectangle: {-1, 0, 1, rx0, rx1 - 1, -(ry1 - 1), -ry0, 1} (d = (0, 1), n =
+ *     (-1, 0), signed dot products as K22 writes them for one vertex), so that tsii_region_crops takes it unchanged; all 0 where there is no
+ *     rectangle, which K23 serves as a row without pixels.
+ *   plane: NULL, or uint8 [h,w]: cleared by the call, then 255 on every pixel of any served B_r.
+ *   The rows behind R are not touched.
+ * How: one workgroup per row; bit planes of the window (a word per 32 pixels) in LDS, the passable plane in the workspace where the window
+ *   is above 768 x 768; the fill sweeps until no word changes, 33 rows and at least a word per sweep.  No allocation, no host
+ *   synchronisation, no floating point, no grid-wide barrier, no global atomics; everything on the caller's stream.
+ * ws: tsii_region_balloons_ws_bytes(h, w, max_regions, reach) bytes (0: arguments refused), 4-byte aligned; it depends on the size
+ *   arguments only, needs nothing cleared beforehand and holds nothing a later call depends on.  Its last max_regions int32 words are a
+ *   debug record: the sweeps the fill of each served row took.  rect is 8-byte aligned.
+ * Refused (non-zero return, tsii_last_error, nothing written): h or w outside 1..32767 (h*w <= 2^31 - 2 follows); max_regions < 1; ring
+ *   outside 1..8; tol outside 0..255; reach < ring or > 512; a NULL pointer other than plane; a misaligned rect (8 bytes), balloon or ws (4 bytes).
+ * Every box or count read from table or n_regions is clamped to the page and to max_regions before use: a table that does not belong to
+ *   the labels gives wrong numbers, never an access outside the buffers. */
+size_t tsii_region_balloons_ws_bytes(int h, int w, int max_regions, int reach);
+int tsii_region_balloons(const uint8_t* page, const uint8_t* text, const int* labels, int h, int w, const int* table, const int* n_regions,
+                         int max_regions, int ring, int tol, int reach, int* balloon, int64_t* rect, uint8_t* plane, void* ws, void* stream);
 
 #ifdef __cplusplus
 }

@@ -13,8 +13,8 @@ from .loss import BinaryFocalLoss, FeatureExtractor, InpaintingLoss, gram_matrix
 from .recipes import InpaintingRecipe, SegmentationRecipe  # noqa: F401,E402
 from .ops import activation_storage, set_activation_storage  # noqa: F401,E402
 from .pipeline import TextEraser, plan_fill_windows, resize_page_u8, working_size  # noqa: F401,E402
-from .regions import (FlatFill, RegionCrops, RegionGeometry, RegionHulls, SeededRegions, SmoothFill, TextBlocks, TextRegions, ToneFill,  # noqa: F401,E402
-                      check_crop_args, check_paste_args, check_tone_args, fill_region_hulls, flat_fill_regions, paste_crops, region_crops,
+from .regions import (FlatFill, RegionBalloons, RegionCrops, RegionGeometry, RegionHulls, SeededRegions, SmoothFill, TextBlocks, TextRegions, ToneFill,  # noqa: F401,E402
+                      check_crop_args, check_paste_args, check_tone_args, fill_region_hulls, flat_fill_regions, paste_crops, region_balloons, region_crops,
                       region_geometry, seeded_regions, smooth_fill_regions, text_blocks, text_regions, tone_fill_regions)
 from .fill import HarmonicFill, PatchFill, SeamlessFill, harmonic_fill, patch_fill, seamless_fill  # noqa: F401,E402
 from .metrics import InpaintingMetrics, SegmentationMetrics, evaluate_inpainting, evaluate_segmentation  # noqa: F401,E402

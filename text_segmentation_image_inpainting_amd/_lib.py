@@ -10,7 +10,7 @@ import torch
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("TSII_LIBRARY") or os.path.join(_HERE, "libtsii_hip.so")   # TSII_LIBRARY: another BUILD of csrc/ (A/B measurements)
-ABI_VERSION = 26       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
+ABI_VERSION = 27       # TSII_ABI_VERSION of include/tsii_hip.h this binding was written against
 
 _p, _i, _l, _f, _z = ctypes.c_void_p, ctypes.c_int, ctypes.c_int64, ctypes.c_float, ctypes.c_size_t
 _GEOM = [_i] * 8  # kh kw sh sw ph pw dh dw
@@ -214,6 +214,9 @@ SIGNATURES = {
     "tsii_region_crops": (_i, [_p, _i, _i, _p, _p, _i, _i, _i, _i, _i, _i, _i, _p, _p, _p]),
     # K24 region paste (csrc/paste.hip): the uint8 page in place, int32 info and count and uint8 RGBA slots in, the int64 plan out
     "tsii_region_paste": (_i, [_p, _i, _i, _p, _p, _i, _p, _i, _i, _i, _p, _p]),
+    # K25 region balloons (csrc/balloon.hip): uint8 page / text / plane, int32 labels / table / counts in, int32 balloon rows and int64 rectangles out
+    "tsii_region_balloons_ws_bytes": (_z, [_i, _i, _i, _i]),
+    "tsii_region_balloons": (_i, [_p, _p, _p, _i, _i, _p, _p, _i, _i, _i, _i, _p, _p, _p, _p, _p]),
 }
 
 _LIB = None

@@ -12,6 +12,7 @@ static inline int atomicMax(int* p, int v) { const int o = *p; if (v > o) *p = v
 static inline int atomicCAS(int* p, int expect, int v) { const int o = *p; if (o == expect) *p = v; return o; }
 using ::atomicAdd;                               // the overload below would hide the emulator's own
 static inline unsigned long long atomicAdd(unsigned long long* p, unsigned long long v) { const unsigned long long o = *p; *p = o + v; return o; }
+static inline unsigned long long atomicMax(unsigned long long* p, unsigned long long v) { const unsigned long long o = *p; if (v > o) *p = v; return o; }
 
 }  // namespace tsii
 #endif

@@ -49,9 +49,10 @@ from ._lib import call, ptr
 from .BaseModels import to_nhwc
 from .fill import _seamless_fill, check_sweeps
 from .masks import MaskParts
-from .regions import (ReadBack, RegionCrops, _check_int_range, _flat_regions, _region_crops, _region_geometry, _region_hulls, _region_paste,
-                      _region_seeds, _rgba, _smooth_regions, _text_blocks, _text_regions, _tone_regions, check_block_args, check_crop_args,
-                      check_flat_args, check_geometry_args, check_region_args, check_seed_args, check_smooth_args, check_tone_args)
+from .regions import (ReadBack, RegionBalloons, RegionCrops, _check_int_range, _flat_regions, _region_balloons, _region_crops, _region_geometry,
+                      _region_hulls, _region_paste, _region_seeds, _rgba, _smooth_regions, _text_blocks, _text_regions, _tone_regions,
+                      balloon_rect_rows, check_balloon_args, check_block_args, check_crop_args, check_flat_args, check_geometry_args,
+                      check_region_args, check_seed_args, check_smooth_args, check_tone_args)
 
 
 class TileGrid(NamedTuple):
@@ -294,7 +295,7 @@ def _eval_mode(*nets):
 # yet), "joined" (the read-back tensor is formed; "counts_d2h" behind it is the copy alone) and "planned" (the host has selected the
 # tiles or planned the windows and uploaded their small index tensors).
 STAGE_MARKS = ("start", "upload", "resize", "page_tiles_norm", "segmenter", "tiles_text_mask", "plane_up", "regions", "blocks", "seeds", "geometry",
-               "hulls", "flat", "smooth", "tone", "crops", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
+               "hulls", "balloon", "flat", "smooth", "tone", "crops", "joined", "counts_d2h", "planned", "page_tiles_fill", "page_windows_fill", "filler", "blend",
                "compose_page_u8", "compose_page_windows_u8", "download")
 
 
@@ -434,6 +435,21 @@ class TextEraser:
     words) with the helpers ``crop``, ``quad``, ``to_page`` and ``scale``; ``last_stats`` gains ``crops = n``.  In page pixels, also
     behind ``seg_long_side``.  Still one synchronisation.  ``None`` (the default): none of this runs.
 
+    ``balloon=T`` (an integer 0..255; turns the regions path on as well): where a translation has room.  For every table row -- with ``group``
+    every block -- the ring within ``balloon_ring`` (1..8) pixels of the lettering gives a colour, as for ``flat``; where the ring is of one
+    colour within ``T`` the BALLOON is the flood fill (4-connected) from the lettering over the page pixels within ``T`` of that colour that
+    are no text, inside the row's box grown by ``balloon_reach`` (``balloon_ring``..512) pixels; other rows' lettering is an obstacle.  The
+    stage runs on the RAW page and on the labels, the table and the text plane behind ``min_area``, the blocks, the seeds and the geometry,
+    in front of the routes: the plane it reads holds every kept region and nothing has been painted ("K25" of ``include/tsii_hip.h``).  Its
+    mark stands behind ``hulls``: with ``hull`` it reads a copy of the plane taken in front of the fill, so the hulls are no obstacle.
+    ``last_regions`` gains ``balloons``, a ``RegionBalloons`` (``status``, ``is_balloon``, ``is_open``, ``colour``, ``ring_pixels``, ``area``,
+    ``box``, ``anchor``, ``inner``: the largest upright rectangle inside the balloon around the block's centre, and ``rect``: the same in
+    the layout ``region_crops`` takes); its 16 words per row ride the one read-back as the last ``16 * max_regions`` words.  ``last_stats``
+    gains ``balloons`` and ``open_balloons``.  The rectangles stay on the device as ``last_balloon_rect`` (int64 ``[max_regions, 8]``), and
+    ``typeset(page, slots, into="balloon")`` lays the slots into them instead of into the old lettering's footprint.  A row whose window
+    would exceed 1024 pixels a side has no balloon (status bit 8).  In page pixels, also behind ``seg_long_side``.  Still one
+    synchronisation.  ``None`` (the default): none of this runs.
+
     ``blend=True``: seamless (gradient-domain, Poisson) composition of what the filler paints.  An inpainting net reproduces structure well
     and absolute level badly: its patch is plausible and a shade lighter or darker than the page around it.  The filler returns the whole
     tile, so its error ``x - clamp(out, 0, 1)`` is known at the valid pixels around every hole; between the filler and compose the harmonic
@@ -456,7 +472,8 @@ class TextEraser:
                  threshold=0.5, dilate=3, tile_batch=8, device=None, skip_blank_tiles=True, min_area=0, connectivity=8, regions=False,
                  max_regions=4096, seg_long_side=None, hull=False, pack=False, flat=None, flat_ring=3, group=None, smooth=None,
                  smooth_ring=3, smooth_sweeps=8, tone=None, tone_ring=8, tone_period=12, seed=None, min_seeds=1, blend=False, blend_sweeps=8,
-                 geometry=False, max_vertices=64, crops=None, max_crops=64, crop_orient="upright", crop_fill=255, crop_supersample=4):
+                 geometry=False, max_vertices=64, crops=None, max_crops=64, crop_orient="upright", crop_fill=255, crop_supersample=4,
+                 balloon=None, balloon_ring=3, balloon_reach=256):
         tile_grid(1, 1, tile, halo)                     # validates tile / halo
         if not 0.0 < float(threshold) < 1.0:
             raise ValueError(f"threshold {threshold} must be a probability in (0, 1)")
@@ -500,8 +517,11 @@ class TextEraser:
         self.crops = None if crops is None else (int(crops[0]), int(crops[1]))
         self.max_crops, self.crop_orient, self.crop_fill, self.crop_supersample = int(max_crops), crop_orient, int(crop_fill), int(crop_supersample)
         self.geometry, self.max_vertices = bool(geometry) or self.crops is not None, int(max_vertices)
+        if balloon is not None or (balloon_ring, balloon_reach) != (3, 256):
+            check_balloon_args(0 if balloon is None else balloon, balloon_ring, balloon_reach)
+        self.balloon, self.balloon_ring, self.balloon_reach = None if balloon is None else int(balloon), int(balloon_ring), int(balloon_reach)
         self.regions = (bool(regions) or self.min_area > 1 or self.hull or self.pack or self.group is not None or self.routes
-                        or self.seed is not None or self.geometry)
+                        or self.seed is not None or self.geometry or self.balloon is not None)
         self.segmenter, self.filler = segmenter, filler
         self.tile, self.halo, self.dilate, self.tile_batch = int(tile), int(halo), int(dilate), int(tile_batch)
         self.threshold, self.skip_blank_tiles = float(threshold), bool(skip_blank_tiles)
@@ -519,6 +539,8 @@ class TextEraser:
         self.last_crops = None                          # its crops (``crops`` only): uint8 ``[max_crops, ch, cw, 3]``, left on the device
         self.last_crop_info = None                      # their info, int32 ``[max_crops * 10]``, and (``_crop_rows``) the word of the row count, left on the device: what ``typeset`` reads
         self._crop_rows = self._crop_page = None
+        self.last_balloon_rect = None                   # its balloons' inner rectangles (``balloon`` only): int64 ``[max_regions, 8]``, and (``_balloon_rows``) the device pair of the row count, left on the device: what ``typeset(into="balloon")`` reads
+        self._balloon_rows = None
         self.last_route_labels = None                   # the int32 label plane the flat, smooth and tone stages worked on, left on the device; None unless one of them is enabled
 
     # A page runs in three phases over one PageState: _enqueue, _read_back (the one synchronisation) and _finish with _download behind
@@ -553,7 +575,8 @@ class TextEraser:
         """the page's read-back tensor: what rides where in it"""
         return ReadBack(g.count, self.max_regions, self.hull, self.group is not None, self.flat is not None, self.smooth is not None,
                         self.tone is not None, regions=self.regions, seeds=self.seed is not None,
-                        geometry=self.max_vertices if self.geometry else 0, crops=self.max_crops if self.crops is not None else 0)
+                        geometry=self.max_vertices if self.geometry else 0, crops=self.max_crops if self.crops is not None else 0,
+                        balloons=self.balloon is not None)
 
     def _route(self, name, src, text, g, labels, own, mask_u8):
         """the flat, smooth or tone stage: fill the regions it takes and take them out of the text plane in place -> the filled page (a new
@@ -627,7 +650,7 @@ class TextEraser:
     def _enqueue_regions(self, st):
         """the regions path of phase 1, in place on ``st.text``: labelling, blocks, seeds, hulls and the flat, smooth and tone stages"""
         g, text, lay = st.g, st.text, self._layout(st.g)
-        second = whole = geometry = info = None
+        second = whole = geometry = info = balloons = None
         if self.group is None:
             self.last_labels, first = _text_regions(text, self.connectivity, self.min_area, self.max_regions, g, tail=lay.tail + lay.extra)
             if lay.seeded:                              # the seeds' room rides behind the first tensor
@@ -647,9 +670,17 @@ class TextEraser:
         if self.geometry:                               # of the labelled pixels, in front of the hulls: the fill then covers the same polygons
             geometry = _region_geometry(self.last_labels, first[lay.routes.table], first[lay.n_regions], self.max_regions, self.max_vertices)
             self._mark("geometry")
+        plain = text                                    # the plane of every kept region, as the labelling left it
         if self.hull:
+            if self.balloon is not None:                # the hulls fill the plane in place: the balloon stage behind them reads a copy of it as it is now
+                plain = text.clone()
             _region_hulls(text, self.last_labels, first, self.max_regions, g)
             self._mark("hulls")
+        if self.balloon is not None:                    # on the raw page and the plane of every kept region: nothing has been filled or painted there
+            balloons, self.last_balloon_rect, _, _ = _region_balloons(st.page_d, plain, self.last_labels, first[lay.routes.table], first[lay.n_regions],
+                                                                      self.max_regions, self.balloon_ring, self.balloon, self.balloon_reach)
+            self._balloon_rows = first[lay.n_regions]
+            self._mark("balloon")
         if self.routes:
             labels, own = self.last_labels, first
             if self.hull:                               # hull pixels carry no label: the filled plane is labelled once more, for all stages
@@ -665,7 +696,7 @@ class TextEraser:
                                                   self.max_crops, self.crop_orient, self.crop_fill, self.crop_supersample)
             self.last_crop_info, self._crop_rows, self._crop_page = info, first[lay.n_regions][1:], (g.h, g.w)
             self._mark("crops")
-        st.read_back = lay.join(first, second, whole, geometry, info)
+        st.read_back = lay.join(first, second, whole, geometry, info, balloons)
 
     def _seed_plane(self, st):
         """the seed plane on the page's grid: ``logit > logit_of(seed)``, not dilated, through the kernels that made the text plane"""
@@ -685,6 +716,9 @@ class TextEraser:
             self.last_regions.update(read.stages)
             if read.crop_info is not None:
                 self.last_regions["crops"] = RegionCrops(self.last_crops[:len(read.crop_info)], read.crop_info)
+            if read.balloon_rows is not None:           # the rectangles are a function of the rows: nothing more is read back
+                rect = balloon_rect_rows(read.balloon_rows)
+                self.last_regions["balloons"] = RegionBalloons(None, read.balloon_rows, rect, None, read.table)
         return read
 
     def _finish(self, st, read):
@@ -733,6 +767,9 @@ class TextEraser:
             self.last_stats.update(seed_dropped=read.seed_dropped, seed_dropped_pixels=read.seed_dropped_pixels)
         if self.crops is not None:
             self.last_stats.update(crops=len(read.crop_info))
+        if self.balloon is not None:
+            b = self.last_regions["balloons"]
+            self.last_stats.update(balloons=int(b.is_balloon.sum()), open_balloons=int((b.is_balloon & b.is_open).sum()))
         if self.pack:
             self.last_stats.update(packed=windows is not None, windows=self.last_stats["selected"],
                                    grid_selected=len(selected) if any_text else 0)
@@ -757,16 +794,24 @@ class TextEraser:
             return [self._erase(p) for p in page]
         return self._erase(page)
 
-    def typeset(self, page_u8, slots, supersample=4):
+    def typeset(self, page_u8, slots, supersample=4, into="block"):
         """Lay ``slots`` -- pictures drawn into the slots of the latest page's crops, ``[n <= max_crops, ch, cw, 4]`` uint8 straight RGBA, or
         ``[..., 3]``, which is opaque; numpy or torch, host or device -- onto ``page_u8`` (``[H, W, 3]`` uint8, normally the ``clean`` the call
         just returned) where the crops were cut out: the page with its new lettering.  ``page_u8`` is not modified; the result is a copy of
         the same kind, on the same device.  Row ``r`` goes where ``last_regions["crops"]`` says slot ``r`` came from, a later row over an
         earlier one, rows without a crop paste nothing and no slots give the copy; antialiased, with up to ``supersample`` (1..4) squared sub-samples per page pixel
         (``paste_crops``, "K24: region paste").  The ``info`` of the crops stage is still on the device: nothing is uploaded but the slots (and
-        a host page), and nothing is read back.  A call of its own behind ``__call__``: the page's course is not touched."""
+        a host page), and nothing is read back.  A call of its own behind ``__call__``: the page's course is not touched.
+
+        ``into="balloon"`` (needs ``balloon=T`` as well) lays slot ``r`` into the inner rectangle of row ``r``'s balloon instead, the room the
+        page has for a translation: the ``info`` is derived at call time from ``last_balloon_rect`` on the device (``tsii_region_crops`` into a
+        scratch batch, upright) and the paste runs with that; a row without a balloon pastes nothing."""
+        if into not in ("block", "balloon"):
+            raise ValueError(f"into {into!r} must be 'block' or 'balloon'")
         if self.crops is None:
             raise RuntimeError("typeset needs the crops stage: TextEraser(crops=(ch, cw))")
+        if into == "balloon" and self.balloon is None:
+            raise RuntimeError("typeset(into='balloon') needs the balloon stage: TextEraser(balloon=T)")
         if self.last_crop_info is None:
             raise RuntimeError("typeset needs a page: no page has been erased yet")
         p = _page_tensor(page_u8)
@@ -779,7 +824,11 @@ class TextEraser:
         if tuple(p.shape[:2]) != self._crop_page:
             raise ValueError(f"page of {tuple(p.shape[:2])} pixels; the crops are those of a page of {self._crop_page}")
         out = p.to(self.device, copy=True).contiguous()
-        if sl.shape[0] > 0:                             # no slots: the copy, as paste_crops has it
+        if sl.shape[0] > 0 and into == "balloon":
+            _, info = _region_crops(out, self.last_balloon_rect, self._balloon_rows, self.max_regions, self.crops, self.max_crops, "upright",
+                                    self.crop_fill, 1)
+            _region_paste(out, info, self._crop_rows, _rgba(sl.to(self.device)), supersample)
+        elif sl.shape[0] > 0:                           # no slots: the copy, as paste_crops has it
             _region_paste(out, self.last_crop_info, self._crop_rows, _rgba(sl.to(self.device)), supersample)
         return out.cpu().numpy() if isinstance(page_u8, np.ndarray) else out.to(page_u8.device)
 

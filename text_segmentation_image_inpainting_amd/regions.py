@@ -40,6 +40,11 @@ region geometry"): the oriented box a translation is typeset into, and the text 
 ``paste_crops`` is the way back: a batch of RGBA pictures, one per slot, is laid onto a page along the rectangles the crops' ``info`` names,
 antialiased and alpha-blended in row order (``tsii_region_paste``, ``csrc/paste.hip``; "K24: region paste"): the translated lettering on the
 cleaned page.
+
+``region_balloons`` says where a translation has room: for every region (with ``gap``: every block) the speech balloon around it -- the
+flood fill from the lettering over the colour of its ring --, its area and box, whether it is closed, and the largest upright rectangle
+inside it around the block's centre, as a ``rect`` row ``region_crops`` and ``paste_crops`` take (``tsii_region_balloons``,
+``csrc/balloon.hip``; "K25: region balloons").
 """
 from typing import NamedTuple
 
@@ -222,8 +227,76 @@ class RegionCrops(NamedTuple):
         return paste_crops(page_u8, slots, self.info, **kw)
 
 
+class RegionBalloons(NamedTuple):
+    """The speech balloon of every table row ("K25" of ``include/tsii_hip.h``).  ``regions``: the ``TextRegions`` (with ``gap``: the
+    ``TextBlocks``) of the input, None inside ``TextEraser``.  ``rows``: numpy int32 ``[n, 16]``, ``(status, n, colour r, g, b, area, by0,
+    bx0, by1, bx1, ay, ax, ry0, rx0, ry1, rx1)`` per row.  ``rect``: numpy int64 ``[n, 8]``, the inner rectangle in ``RegionGeometry.rect``'s
+    layout (all 0 without one): ``region_crops`` and ``paste_crops`` take it as it is.  ``plane``: uint8 ``[H, W]`` of 0 / 255, the union of
+    the balloons, or None.  ``table_rows``: the table where ``regions`` is None.  The properties are plain numpy on ``rows``."""
+    regions: object
+    rows: np.ndarray
+    rect: np.ndarray
+    plane: object = None
+    table_rows: np.ndarray = None
+
+    @property
+    def table(self):
+        """numpy int32 ``[n, 6]``: the region (block) table the rows belong to"""
+        return self.table_rows if self.regions is None else self.regions.table
+
+    @property
+    def status(self):
+        """int32 ``[n]``: bit 1 no ring, 2 the ring is not of one colour, 4 open, 8 the window is too large, 16 no pixels of its own"""
+        return self.rows[:, 0]
+
+    @property
+    def is_balloon(self):
+        """bool ``[n]``: the row has a balloon (open or closed): none of the bits 1, 2, 8 and 16"""
+        return (self.rows[:, 0] & (1 | 2 | 8 | 16)) == 0
+
+    @property
+    def is_open(self):
+        """bool ``[n]``: the fill ran to the end of its reach (lettering on open page)"""
+        return (self.rows[:, 0] & 4) != 0
+
+    @property
+    def colour(self):
+        """uint8 ``[n, 3]``: the rounded mean of the ring"""
+        return self.rows[:, 2:5].astype(np.uint8)
+
+    @property
+    def ring_pixels(self):
+        return self.rows[:, 1]
+
+    @property
+    def area(self):
+        """int32 ``[n]``: the balloon's pixels, the row's own lettering included; 0 without a balloon"""
+        return self.rows[:, 5]
+
+    @property
+    def box(self):
+        """int32 ``[n, 4]``: ``y0, x0, y1, x1`` of the balloon, half-open"""
+        return self.rows[:, 6:10]
+
+    @property
+    def anchor(self):
+        """int32 ``[n, 2]``: ``(y, x)`` of the pixel of the lettering nearest the centre of its box"""
+        return self.rows[:, 10:12]
+
+    @property
+    def inner(self):
+        """int32 ``[n, 4]``: ``y0, x0, y1, x1``, half-open, of the largest upright rectangle inside the balloon that holds the anchor"""
+        return self.rows[:, 12:16]
+
+    def crops(self, page_u8, size, **kw):
+        """``region_crops(page_u8, self.rect, size, **kw)``: the inner rectangles as slots to render into; the ``RegionCrops`` has ``crop(r)``
+        and ``paste(page, slots)``"""
+        return region_crops(page_u8, self.rect, size, **kw)
+
+
 CROP_ORIENTS = {"upright": 0, "long": 1}
 CROP_INFO = 10                                              # int32 words of info per slot
+BALLOON_WORDS = 16                                          # int32 words per row of tsii_region_balloons
 
 
 def _check_int_range(name, value, lo, hi):
@@ -299,6 +372,7 @@ class PageRead(NamedTuple):
     ``seed_dropped`` / ``seed_dropped_pixels`` (the rows ``tsii_region_seeds`` took out, their summed area): with ``seeds``, else None.
     ``n_vertices`` / ``vertices`` / ``rect``: with ``geometry``, of each table row (``RegionGeometry``), else None.
     ``crop_info``: with ``crops``, the ``info`` of the first ``min(rows, max_crops)`` table rows (``RegionCrops``), else None.
+    ``balloon_rows``: with ``balloons``, int32 ``[rows, 16]`` of each table row (``RegionBalloons.rows``), else None.
     Without the regions path all but ``counts`` is None."""
     counts: np.ndarray
     table: np.ndarray = None
@@ -320,6 +394,7 @@ class PageRead(NamedTuple):
     vertices: np.ndarray = None
     rect: np.ndarray = None
     crop_info: np.ndarray = None
+    balloon_rows: np.ndarray = None
 
 
 class ReadBack:
@@ -333,10 +408,11 @@ class ReadBack:
     tensor -- with ``group`` the blocks' ``whole`` -- is allocated with (``seed_room``), so that nothing in front of it moves.  With
     ``geometry`` (the ``max_vertices`` of the stage; 0: off) the tensor of ``_region_geometry`` (``GeometryLayout``) rides behind all of
     that, as the last ``geometry.words`` words.  With ``crops`` (the ``max_crops`` of the stage; 0: off) the ``info`` of ``_region_crops``
-    rides behind that again: the LAST ``10 * max_crops`` words."""
+    rides behind that again: ``10 * max_crops`` words.  With ``balloons`` the rows of ``_region_balloons`` are the LAST ``16 * max_regions``
+    words; without it the tensor has the length it had before that stage existed."""
 
     def __init__(self, nt, max_regions, hull=False, group=False, flat=False, smooth=False, tone=False, regions=True, seeds=False, geometry=0,
-                 crops=0):
+                 crops=0, balloons=False):
         n = int(max_regions)
         self.routes = RouteLayout(nt, n, flat, smooth, tone)
         self.regions, self.hull, self.group = bool(regions), bool(hull), bool(group)
@@ -358,6 +434,9 @@ class ReadBack:
         self.crops = int(crops) if crops and self.geometry is not None else 0
         self.crop_words = slice(self.words, self.words + CROP_INFO * self.crops)
         self.words = self.crop_words.stop
+        self.balloons = bool(balloons) and self.regions
+        self.balloon_words = slice(self.words, self.words + (BALLOON_WORDS * n if self.balloons else 0))
+        self.words = self.balloon_words.stop
 
     def seed_room(self, whole):
         """(members, room) on the device for ``_region_seeds``: ``whole`` is the first labelling's tensor as allocated, ``[first | members,
@@ -366,11 +445,12 @@ class ReadBack:
         assert self.seeded and whole.numel() == self.first.stop + (n + 1 if self.group else 0) + self.extra
         return (whole[self.first.stop:self.first.stop + n] if self.group else None), whole[whole.numel() - self.extra:]
 
-    def join(self, first, second=None, whole=None, geometry=None, crops=None):
-        """``_join`` of the stages' tensors, with the tensor of ``_region_geometry`` and the ``info`` of ``_region_crops`` behind it where
-        those stages ran"""
+    def join(self, first, second=None, whole=None, geometry=None, crops=None, balloons=None):
+        """``_join`` of the stages' tensors, with the tensor of ``_region_geometry``, the ``info`` of ``_region_crops`` and the rows of
+        ``_region_balloons`` behind it where those stages ran"""
         joined = self._join(first, second, whole)
-        return joined if geometry is None else torch.cat([joined, geometry] if crops is None else [joined, geometry, crops])
+        parts = [joined] + [t for t in (geometry, crops if geometry is not None else None, balloons) if t is not None]
+        return joined if len(parts) == 1 else torch.cat(parts)
 
     def _join(self, first, second=None, whole=None):
         """the tensor to copy, from what the stages left on the device: ``first``, ``second`` (None where the route stages worked on
@@ -404,6 +484,8 @@ class ReadBack:
             read = read._replace(**dict(zip(("n_vertices", "vertices", "rect"), self.geometry.unpack(host[self.geometry_words], n))))
         if self.crops:
             read = read._replace(crop_info=host[self.crop_words].reshape(self.crops, CROP_INFO)[:min(n, self.crops)].copy())
+        if self.balloons:
+            read = read._replace(balloon_rows=host[self.balloon_words].reshape(self.routes.max_regions, BALLOON_WORDS)[:n].copy())
         return read
 
 
@@ -578,6 +660,44 @@ def _rgba(slots):
     if slots.shape[3] == 4:
         return slots.contiguous()
     return torch.cat([slots, torch.full_like(slots[..., :1], 255)], dim=3)
+
+
+def balloon_rect_rows(rows):
+    """balloon rows ``[n, 16]`` -> the ``rect`` rows ``tsii_region_balloons`` writes beside them, int64 ``[n, 8]``: they are a function of the
+    inner rectangle, all 0 where there is none"""
+    rows = np.asarray(rows).astype(np.int64).reshape(-1, BALLOON_WORDS)
+    ry0, rx0, ry1, rx1 = rows[:, 12], rows[:, 13], rows[:, 14], rows[:, 15]
+    rect = np.stack([np.full_like(ry0, -1), np.zeros_like(ry0), np.ones_like(ry0), rx0, rx1 - 1, -(ry1 - 1), -ry0, np.ones_like(ry0)], axis=1)
+    rect[ry1 <= ry0] = 0
+    return rect
+
+
+def check_balloon_args(tol, ring, reach):
+    _check_int_range("balloon tolerance", tol, 0, 255)
+    _check_int_range("balloon ring", ring, 1, 8)
+    _check_int_range("balloon reach", reach, ring, 512)
+
+
+def _region_balloons(page, text, labels, table, n_regions, max_regions, ring, tol, reach, plane=False):
+    """``tsii_region_balloons`` on the current stream, behind ``_text_regions`` or ``_text_blocks``: ``page`` (uint8 ``[h, w, 3]``), ``text``,
+    ``labels``, ``table`` (the device words of the table) and ``n_regions`` (the device pair) are read only -> (rows int32 ``[16 *
+    max_regions]``, rect int64 ``[max_regions, 8]``, plane uint8 ``[h, w]`` or None, sweeps int32 ``[max_regions]``: a view of the workspace's
+    debug words, valid until the next call that takes a workspace) on the device; the rows behind those served are 0."""
+    h, w = int(text.shape[0]), int(text.shape[1])
+    n = int(max_regions)
+    assert page.dtype == torch.uint8 and page.is_contiguous() and tuple(page.shape) == (h, w, 3) and page.device == text.device
+    assert text.dtype == torch.uint8 and text.is_contiguous() and labels.shape == text.shape and labels.dtype == torch.int32 and labels.is_contiguous()
+    assert table.dtype == torch.int32 and table.numel() >= 6 * n
+    nbytes = int(_lib.lib().tsii_region_balloons_ws_bytes(h, w, n, int(reach)))
+    if nbytes == 0:
+        raise ValueError(f"region balloons: a page of {h} x {w} pixels (sides up to 32767), {max_regions} regions, reach {reach}: out of range")
+    rows = torch.zeros((BALLOON_WORDS * n,), dtype=torch.int32, device=text.device)
+    rect = torch.zeros((n, 8), dtype=torch.int64, device=text.device)
+    out_plane = torch.empty((h, w), dtype=torch.uint8, device=text.device) if plane else None
+    ws = ops._ws(nbytes, text)
+    call("tsii_region_balloons", ptr(page), ptr(text), ptr(labels), h, w, ptr(table), ptr(n_regions), n, int(ring), int(tol), int(reach), ptr(rows),
+         ptr(rect), ptr(out_plane), ptr(ws), _lib.stream())
+    return rows, rect, out_plane, ws.view(torch.int32)[nbytes // 4 - n:nbytes // 4]
 
 
 def _region_seeds(text, labels, seed, packed, room, max_regions, min_seeds, members=None, grid=None):
@@ -895,6 +1015,41 @@ def region_geometry(mask_u8, connectivity=8, min_area=0, max_regions=4096, max_v
     else:
         regions = TextBlocks(_like(plane * 255, mask_u8), _like(labels, mask_u8), r.table, r.members, r.found, r.kept, r.components)
     return RegionGeometry(regions, r.n_vertices, r.vertices, r.rect)
+
+
+def region_balloons(page_u8, mask_u8, tol, ring=3, reach=256, connectivity=8, min_area=0, gap=None, return_plane=False, max_regions=4096,
+                    device=None) -> RegionBalloons:
+    """The speech balloon around every text region, and the room for a translation inside it.  ``page_u8``: ``[H, W, 3]`` uint8; ``mask_u8``:
+    ``[H, W]`` uint8, non-zero = text (the 255 masks ``TextEraser`` returns work directly); numpy or torch, host or device, sides up to
+    32767, neither is modified.  Regions below ``min_area`` are dropped first, as in ``text_regions``; with ``gap`` (1..64) the regions are
+    grouped into blocks first, as in ``text_blocks``, and ``regions`` is the ``TextBlocks``.  Per row: the ring within ``ring`` (1..8) pixels
+    of the lettering gives the colour, as in ``flat_fill_regions``; where it is of one colour within ``tol`` (0..255) the balloon is the
+    flood fill (4-connected) from the lettering over the pixels within ``tol`` of that colour that are no text, inside the row's box grown
+    by ``reach`` (``ring``..512) pixels; other rows' lettering is an obstacle.  ``is_open`` says that the fill ran to the end of its reach
+    (lettering on open page), ``inner`` is the largest upright rectangle in the balloon around the block's centre and ``rect`` the same in
+    the layout ``region_crops`` takes.  A row whose window would exceed 1024 pixels a side gets status bit 8 and no balloon.
+    ``plane`` (with ``return_plane``) and the labels come back the same kind and on the same device as ``mask_u8``; one synchronisation
+    (the read-back of the counts, the table and the balloon rows).  Host arguments are computed on ``device`` (default ``cuda:0``)."""
+    check_region_args(connectivity, min_area, max_regions)
+    check_balloon_args(tol, ring, reach)
+    if gap is not None:
+        check_block_args(gap)
+    page, plane = _page_and_plane(page_u8, mask_u8, device)
+    rb = ReadBack(0, max_regions, group=gap is not None, balloons=True)
+    if gap is None:
+        labels, first = _text_regions(plane, connectivity, min_area, max_regions)
+        whole = None
+    else:
+        every, counts = _text_regions(plane, connectivity, 0, 0)
+        labels, first, whole = _text_blocks(plane, every, counts, gap, min_area, max_regions)
+    rows, _, filled, _ = _region_balloons(page, plane, labels, first[rb.routes.table], first[rb.n_regions], max_regions, ring, tol, reach,
+                                             plane=return_plane)
+    r = rb.unpack(rb.join(first, None, whole, balloons=rows).cpu().numpy())
+    if gap is None:
+        regions = TextRegions(_like(labels, mask_u8), r.table, r.found, r.kept, r.truncated)
+    else:
+        regions = TextBlocks(_like(plane * 255, mask_u8), _like(labels, mask_u8), r.table, r.members, r.found, r.kept, r.components)
+    return RegionBalloons(regions, r.balloon_rows, balloon_rect_rows(r.balloon_rows), None if filled is None else _like(filled, mask_u8))
 
 
 def region_crops(page_u8, rect, size, n_rows=None, orient="upright", fill=255, supersample=4, device=None) -> RegionCrops:

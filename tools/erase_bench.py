@@ -4,7 +4,7 @@
     python tools/erase_bench.py [--size 1170 1654] [--tile 512 --halo 64] [--repeats 10 --warmup 3] [--text-fraction 0.1]
                                 [--min-area N [--connectivity 8]] [--hull] [--all-text] [--seg-long-side N] [--pack]
                                 [--bubbles SHARE] [--flat T [--flat-ring N]] [--ramps SHARE] [--smooth T] [--tones SHARE] [--tone T [--tone-ring N] [--tone-period N]]
-                                [--blend [--blend-sweeps N]] [--geometry [--max-vertices N]]
+                                [--blend [--blend-sweeps N]] [--geometry [--max-vertices N]] [--balloon T [--balloon-ring N] [--balloon-reach N]]
                                 [--crops HxW [--crop-orient long] [--max-crops N]]
 
 Stages: upload, tsii_page_tiles_norm, segmenter, tsii_tiles_text_mask, counts read-back, tsii_page_tiles_fill, filler,
@@ -68,6 +68,10 @@ grows the read-back, so ``geometry_ab`` runs the whole page with and without it,
 into a slot of H x W pixels, behind the flat / smooth / tone stages) with its own pair of events; ``regions`` then reports ``crops`` (rows
 served), ``crop_pixels`` (their pixels) and ``crop_subsamples`` (the bilinear samples behind them).  ``crops_ab`` runs the whole page with
 and without it, alternating, in the same process, as ``geometry_ab`` does.
+``--balloon T`` (turns the regions stage on; not to be confused with ``--bubbles``, which draws the page) adds the ``balloon`` stage
+(tsii_region_balloons: per row the flood fill over the ring's colour, its area, box and open flag and the largest upright rectangle inside
+it), timed between its marks; ``balloon_ab`` runs the whole page with and without it, alternating, in the same process, and reports the
+read-back's growth and the sweeps the fill took per row (the debug words of the stage's workspace).
 ``--typeset`` (needs ``--crops``) times ``TextEraser.typeset`` behind the page, with the page's own crops as opaque slots: ``typeset`` reports
 ``call_ms`` (HIP events around the whole call on a device page: the copy of the page, the alpha plane and tsii_region_paste), ``kernels_ms``
 (events around tsii_region_paste alone; compare with the ``crops`` stage of the same run), ``page_ms`` (the page on the host clock without and
@@ -167,6 +171,9 @@ def main(argv=None):
     ap.add_argument("--crops", default=None, metavar="HxW", help="time the crops stage (tsii_region_crops) into slots of H x W pixels; turns --geometry on")
     ap.add_argument("--crop-orient", default="upright", choices=["upright", "long"])
     ap.add_argument("--max-crops", type=int, default=64, metavar="N", help="slots with --crops")
+    ap.add_argument("--balloon", type=int, default=None, metavar="T", help="time the balloon stage (tsii_region_balloons) at tolerance T (0..255)")
+    ap.add_argument("--balloon-ring", type=int, default=3, metavar="N", help="ring width of the balloon stage (1..8)")
+    ap.add_argument("--balloon-reach", type=int, default=256, metavar="N", help="pixels the balloon's window reaches beyond the block's box (ring..512)")
     ap.add_argument("--typeset", action="store_true", help="time TextEraser.typeset (tsii_region_paste) with the page's own crops as opaque slots; needs --crops")
     ap.add_argument("--all-text", action="store_true", help="the whole page is text: one component")
     ap.add_argument("--seg-long-side", type=int, default=None, help="segment at working_size(H, W, N); times the resize and plane_up stages")
@@ -236,16 +243,17 @@ def main(argv=None):
     with_seeds = args.seed is not None
     crop_size = None if args.crops is None else tuple(int(v) for v in args.crops.lower().split("x"))
     args.geometry = args.geometry or crop_size is not None
-    with_regions = args.min_area > 0 or args.hull or args.pack or with_blocks or with_routes or with_seeds or args.geometry
+    with_regions = args.min_area > 0 or args.hull or args.pack or with_blocks or with_routes or with_seeds or args.geometry or args.balloon is not None
 
-    def make(select, geometry=args.geometry, crops=crop_size):
+    def make(select, geometry=args.geometry, crops=crop_size, balloon=args.balloon):
         er = T.TextEraser(seg, fil, tile=args.tile, halo=args.halo, dilate=args.dilate, tile_batch=args.tile_batch,
                           skip_blank_tiles=select, min_area=args.min_area, connectivity=args.connectivity, regions=with_regions,
                           max_regions=args.max_regions, seg_long_side=args.seg_long_side, hull=args.hull, pack=args.pack and select,
                           flat=args.flat, flat_ring=args.flat_ring, group=args.group, smooth=args.smooth, tone=args.tone,
                           tone_ring=args.tone_ring, tone_period=args.tone_period, seed=args.seed, min_seeds=args.min_seeds, blend=args.blend,
                           blend_sweeps=args.blend_sweeps, geometry=geometry, max_vertices=args.max_vertices, crops=crops,
-                          max_crops=args.max_crops, crop_orient=args.crop_orient)
+                          max_crops=args.max_crops, crop_orient=args.crop_orient, balloon=balloon, balloon_ring=args.balloon_ring,
+                          balloon_reach=args.balloon_reach)
         net = er._segment                                  # the segmenter runs and is timed; the blobs stand in for its logits
         er._segment = lambda page_d, grid: (net(page_d, grid), logits_fixed)[1]     # grid is gs: the eraser derives the same working size
         return er
@@ -295,6 +303,10 @@ def main(argv=None):
             if crop_size is not None:
                 ci = read.crop_info.astype(np.int64)
                 region_info.update(crops=len(ci), crop_pixels=int((ci[:, 0] * ci[:, 1]).sum()), crop_subsamples=int((ci[:, 0] * ci[:, 1] * ci[:, 3] ** 2).sum()))
+            if args.balloon is not None:
+                b = eraser.last_regions["balloons"]
+                region_info.update(balloons=stats["balloons"], open_balloons=stats["open_balloons"], balloon_pixels=int(b.area.sum(dtype=np.int64)),
+                                   inner_pixels=int(((b.inner[:, 2] - b.inner[:, 0]) * (b.inner[:, 3] - b.inner[:, 1])).sum(dtype=np.int64)))
             if args.hull:
                 region_info["hull_pixels"] = int(read.hull_area.sum(dtype=np.int64))
             if with_routes:
@@ -521,6 +533,39 @@ def main(argv=None):
         crops_ab = {"page_ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in vals.items()},
                     "d2h_int32_words": words, "slots": [args.max_crops, *crop_size], "orient": args.crop_orient}
 
+    balloon_ab = None
+    if args.balloon is not None:                            # the same page with and without the stage, alternating, in this very process
+        pair = {"with": make(True), "without": make(True, balloon=None)}
+        vals, words = {k: [] for k in pair}, {}
+        for i in range(args.warmup + args.repeats):
+            for k, er in pair.items():
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                er(page)
+                torch.cuda.synchronize()
+                if i >= args.warmup:
+                    vals[k].append((time.perf_counter() - t0) * 1e3)
+        for k, er in pair.items():
+            with torch.no_grad():
+                words[k] = int(er._enqueue(page).read_back.numel())
+        er = pair["with"]                                   # the sweeps per row: the debug words of the stage's workspace, read right behind a call
+        with torch.no_grad():
+            bst = er._enqueue(page)
+            blay = er._layout(bst.g)
+            bfirst = bst.read_back[blay.first]
+            brows, _, _, sweeps = RG._region_balloons(bst.page_d, torch.where(er.last_labels != 0, 1, 0).to(torch.uint8), er.last_labels,
+                                                     bfirst[blay.routes.table], bfirst[blay.n_regions], args.max_regions, args.balloon_ring, args.balloon,
+                                                     args.balloon_reach)
+            n_brows = min(int(bfirst[blay.n_regions][1]), args.max_regions)
+            sweeps = sweeps[:n_brows].cpu().numpy()
+            brows = brows.cpu().numpy().reshape(-1, 16)[:n_brows]
+        swept = sweeps[(brows[:, 0] & 27) == 0]
+        balloon_ab = {"page_ms": {k: {"median": round(statistics.median(v), 4), "min": round(min(v), 4), "max": round(max(v), 4)} for k, v in vals.items()},
+                      "d2h_int32_words": words, "tol": args.balloon, "ring": args.balloon_ring, "reach": args.balloon_reach, "rows": n_brows,
+                      "sweeps": {"rows_filled": int(len(swept)), "min": int(swept.min()) if len(swept) else 0,
+                                 "median": float(np.median(swept)) if len(swept) else 0.0, "max": int(swept.max()) if len(swept) else 0,
+                                 "sum": int(swept.sum())}}
+
     typeset = None
     if args.typeset:                                        # the way back: the page's own crops, opaque, laid onto the cleaned page (tsii_region_paste)
         from text_segmentation_image_inpainting_amd import _lib
@@ -577,6 +622,7 @@ def main(argv=None):
         "tone_period": args.tone_period if with_tone else None,
         "blend": args.blend, "blend_sweeps": args.blend_sweeps if args.blend else None, "blend_split_ms": blend_split,
         "geometry": args.geometry, "geometry_ab": geometry_ab, "crops": args.crops, "crops_ab": crops_ab, "typeset": typeset,
+        "balloon": args.balloon, "balloon_ab": balloon_ab,
         "pack": args.pack, "packed": windows is not None, "filler_tiles": {"grid": n_sel, "sent": n_fill},
         "plan_host_ms": None if not args.pack else {"median": round(statistics.median(r[7] for r in runs), 4),
                                                     "min": round(min(r[7] for r in runs), 4), "max": round(max(r[7] for r in runs), 4)},
